@@ -14,10 +14,16 @@ collective; the only exchange is the max of the step times and the sum of the er
 (gloo, host scalars).  A "step" = one td_decode_device call on the resident batch (demultiplex +
 all iterations + hard decisions).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the
+JSON line (value, ms_per_step, roofline from the timed region's own hipEvents, BER against the
+generated info bits).  Everything that takes a run of its own -- power, pcie_inclusive, cpu_baseline,
+dropin, variants, demod below -- runs only with --full.
+
+Objects on the JSON line (the first always; the others with --full):
   roofline      the turbo kernel against HBM (algorithmic bytes: fp64 LLR in + uint8 bits out
                 per codeword) with durations from hipEvents inside the timed region;
                 `traffic` from the committed rocprofv3 PMC profile of the same config (or null)
+  power, pcie_inclusive   amdsmi board power / clock over the timed region; the host-fed rate
   cpu_baseline  the compiled reference (oracle/_ref/ref_harness: ITTC/log_map.cpp's SISO and loop) on the
                 host cores, rank 0, N=1; the C restatement (oracle/) where that binary is absent
   dropin        what the unchanged ITTC/main.cpp caller gets: TurboDecoding one frame per call through
@@ -61,6 +67,13 @@ def parse(argv=None):
                     help="config 4 strong scaling: --global-batch codewords split over the N ranks")
     ap.add_argument("--global-batch", type=int, default=CONFIG4_GLOBAL, help="total codewords with --strong")
     ap.add_argument("--dump-bits", default="", help="directory: each rank writes its decoded slice (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="directory: the last timed step's hard decisions as DIR/bits.npy (float32; a fixed "
+                         "seeded sample of rows where the batch is larger than the dump's size budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: power sampler, PCIe-inclusive rate, CPU "
+                         "baseline, drop-in latency, variants (other precisions / algorithms / batches, config 5, "
+                         "BER gate), demodulator rates; the options below trim them")
     ap.add_argument("--K", type=int, default=6144)
     ap.add_argument("--iters", type=int, default=8)
     ap.add_argument("--ebn0", type=float, default=1.0)
@@ -227,7 +240,7 @@ def main():
     barrier()
     torch.cuda.synchronize(dev)
 
-    power = PowerSampler(local) if rank == 0 and not a.no_power else None
+    power = PowerSampler(local) if a.full and rank == 0 and not a.no_power else None
     codec.profile(True)   # hipEvents around each kernel, inside the timed region
     if power is not None:
         power.start()
@@ -252,6 +265,8 @@ def main():
     if a.dump_bits:
         os.makedirs(a.dump_bits, exist_ok=True)
         np.save(os.path.join(a.dump_bits, f"bits_rank{rank}_first{first}.npy"), bits.cpu().numpy())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bits, rank, world)
     elapsed, errs, blk = reduce_over_ranks(t1 - t0, errs, blk, world)
     out = summarize(a, world, elapsed, errs, blk, demux_ms, turbo_ms, nlaunch, f1, f2, clock)
     out["workspace_placement"] = placement_record(placement, turbo_ms, a.iters, placement_cost)
@@ -260,21 +275,49 @@ def main():
         power_rec["nj_per_info_bit"] = round(power_rec["socket_w_mean"] / (out["value"] / world) * 1e3, 2)
     out["power"] = power_rec
 
-    if rank == 0 and world == 1 and not a.no_variants:
+    out["full"] = a.full
+    side = a.full and rank == 0 and world == 1   # the measurements beside the headline (--full)
+    if side and not a.no_variants:
         out["pcie_inclusive"] = pcie_inclusive(a, codec, llr, dev, stream)
-    if rank == 0 and world == 1 and a.cpu_sample > 0:
+    if side and a.cpu_sample > 0:
         n = min(a.cpu_sample, a.batch)
         out["cpu_baseline"] = cpu_baseline(a, llr64[:n].cpu().numpy(), bits[:n].cpu().numpy(), f1, f2)
-    if rank == 0 and world == 1 and a.dropin_frames > 0 and not a.window and a.precision == "f64" and a.algo == "logmap":
+    if side and a.dropin_frames > 0 and not a.window and a.precision == "f64" and a.algo == "logmap":
         out["dropin"] = dropin(a, llr64[: a.dropin_frames].cpu().numpy(), f1, f2, local,
                                info=u_d[: a.dropin_frames].cpu().numpy())
-    if rank == 0 and world == 1 and not a.no_variants:
+    if side and not a.no_variants:
         out["variants"] = variants(a, codec, llr64, u_d, f1, f2, dev, stream)
         out["demod"] = demod_rates(a, dev)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 48 << 20   # bytes of float32 a --dump-outputs directory may hold (all ranks together)
+
+
+def dump_rows(B: int, K: int, world: int = 1):
+    """Rows of a rank's [B, K] bits that --dump-outputs keeps: None (all of them) where they fit the
+    rank's share of DUMP_BUDGET as float32, else a fixed sample (PCG64 of SEED, sorted, distinct)."""
+    rows = max(1, DUMP_BUDGET // world // (4 * K))
+    if B <= rows:
+        return None
+    return np.sort(np.random.default_rng(SEED).choice(B, size=rows, replace=False))
+
+
+def dump_outputs(path: str, bits, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path returned in its last step, the hard decisions uint8 [B, K] of
+    td_decode_device, as float32 in path/bits.npy (bits_rank<r>.npy under torchrun).  The frames are
+    srand(SEED)'s, so two builds given the same arguments write the same rows of the same batch."""
+    import torch
+
+    idx = dump_rows(bits.shape[0], bits.shape[1], world)
+    if idx is not None:
+        bits = bits[torch.from_numpy(idx).to(bits.device)]
+    os.makedirs(path, exist_ok=True)
+    name = "bits.npy" if world == 1 else f"bits_rank{rank}.npy"
+    np.save(os.path.join(path, name), bits.to(torch.float32).cpu().numpy())
 
 
 class PowerSampler:

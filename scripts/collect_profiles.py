@@ -1,4 +1,4 @@
-"""Copy a gpu_round.sh run's evidence from gpurun_out/ into profiles/rNN/ (tag given) and refresh
+"""Copy a gpu_round.sh run's evidence from $OUT (default bench_out/) into profiles/rNN/ (tag given) and refresh
 profiles/traffic.json from the two PMC passes (FETCH_SIZE x2 on gfx950, WRITE_SIZE as is).
 Usage: python scripts/collect_profiles.py r01 v9 "kernel description" """
 import csv
@@ -10,7 +10,7 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rnd, tag, desc = sys.argv[1], sys.argv[2], sys.argv[3]
-src = os.path.join(REPO, "gpurun_out")
+src = os.path.join(REPO, os.environ.get("OUT", "bench_out"))
 dst = os.path.join(REPO, "profiles", rnd)
 os.makedirs(dst, exist_ok=True)
 shutil.copy(os.path.join(src, "prof", "kt_kernel_stats.csv"), os.path.join(dst, f"{tag}_kernel_stats.csv"))

@@ -1,13 +1,13 @@
 #!/bin/bash
-# The driver's bench command (one fresh process) and a summary of its JSON line.
+# The full bench (one fresh process; output under $OUT, default bench_out/) and a summary of its JSON line.
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; export OUT=${OUT:-bench_out}; mkdir -p $OUT
 SECONDS=0
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/b.json 2> gpurun_out/b.err
-rc=$?; echo "bench wall ${SECONDS}s rc=$rc"; [ $rc -eq 0 ] || { tail -20 gpurun_out/b.err; exit $rc; }
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/b.json 2> $OUT/b.err
+rc=$?; echo "bench wall ${SECONDS}s rc=$rc"; [ $rc -eq 0 ] || { tail -20 $OUT/b.err; exit $rc; }
 python - <<'PY'
-import json
-d = json.load(open("gpurun_out/b.json"))
+import json, os
+d = json.load(open(os.path.join(os.environ["OUT"], "b.json")))
 r = d["roofline"]
 print("config 2", d["value"], d["ms_per_step"], r["kernel_ms_avg"], r["sclk_ghz"], r["latency_floor"]["frac"],
       d["workspace_placement"].get("launch_over_probe"), d["workspace_placement"].get("peak_held_over_workspace"))

@@ -10,7 +10,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in turbo_decoder_cuda_amd/libvar_*.so; do
-    TD_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 5 --cpu-sample 0 --no-variants \
+    TD_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --full --steps ${STEPS:-100} --warmup 5 --cpu-sample 0 --no-variants \
         --dropin-frames 0 > gpurun_out/pw.json 2> gpurun_out/pw.err || { echo "$lib failed rc=$?"; tail -20 gpurun_out/pw.err; exit 1; }
     python -c "
 import json; d=json.load(open('gpurun_out/pw.json')); p=d.get('power') or {}; r=d['roofline']

@@ -94,6 +94,25 @@ def test_traffic_model_matches_the_pmc_total():
     assert max(m["bytes"], key=m["bytes"].get) == "alpha"
 
 
+def test_dump_rows_is_a_fixed_sample_within_the_budget():
+    """bench.dump_rows (--dump-outputs): every row where the batch fits the dump's budget as float32,
+    else the same sorted, distinct sample on every call; all ranks together stay under 64 MB."""
+    import numpy as np
+
+    import bench
+
+    assert bench.DUMP_BUDGET <= 64 * 10**6
+    assert bench.dump_rows(45, 1024) is None
+    assert bench.dump_rows(bench.DUMP_BUDGET // (4 * 6144), 6144) is None
+    for B, world in ((4096, 1), (32768, 1), (32768, 8)):
+        idx = bench.dump_rows(B, 6144, world)
+        assert world * len(idx) * 6144 * 4 <= bench.DUMP_BUDGET < world * (len(idx) + 1) * 6144 * 4
+        assert idx[0] >= 0 and idx[-1] < B and (np.diff(idx) > 0).all()
+        assert np.array_equal(idx, bench.dump_rows(B, 6144, world))
+    a = bench.parse(["--dump-outputs", "d"])
+    assert a.dump_outputs == "d" and a.full is False and bench.parse(["--full"]).full is True
+
+
 def test_power_sampler_is_inert_without_a_gpu():
     """bench.PowerSampler (board power / clock record of the timed region) never fails a bench:
     with no GPU (or no amdsmi) its record is null."""

@@ -65,6 +65,27 @@ def _gathered(tmp_path):
 
 
 @pytest.mark.timeout(300)
+def test_plain_run_times_its_steps_and_dumps_their_bits(tmp_path):
+    """A plain bench run (no --full): --steps timed steps, ms_per_step on the line, none of the side
+    measurements, and --dump-outputs = the last step's bits as float32, equal to a direct decode of
+    the same frames."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--K", str(K), "--iters", str(ITERS), "--ebn0", str(EBN0), "--batch", "45", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=REPO,
+                       env=dict(os.environ, TD_PLACEMENT_TRIALS="1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["roofline"]["launches_timed"] == 2
+    assert rec["ms_per_step"] > 0 and rec["value"] == pytest.approx(45 * K / rec["ms_per_step"] / 1e3, rel=1e-3)
+    assert rec["full"] is False and rec["power"] is None
+    assert not {"cpu_baseline", "dropin", "variants", "pcie_inclusive", "demod"} & set(rec)
+    assert os.listdir(str(tmp_path)) == ["bits.npy"]
+    got = np.load(os.path.join(str(tmp_path), "bits.npy"))
+    assert got.dtype == np.float32 and got.shape == (45, K)
+    assert np.array_equal(got, _single_decode(45).astype(np.float32))
+
+
+@pytest.mark.timeout(300)
 def test_weak_shards_equal_single_process_decode(tmp_path):
     rec = _run_ranks(tmp_path, ["--batch", "45"])
     assert rec["n_gpus"] == 2 and rec["config"]["global_batch"] == 90 and rec["scaling"] == "weak"
