@@ -3,6 +3,7 @@ product is a plain C-ABI shared library (include/turbo_mi355x.h)."""
 from __future__ import annotations
 
 import concurrent.futures
+import glob
 import os
 import subprocess
 import sys
@@ -105,9 +106,10 @@ def build(force: bool = False, verbose: bool = False, extra: bool = True) -> Non
     takes the speculation's exact redo in, for test_alpha_speculation_redo_path_is_exact; and the
     stamps build for scripts/diag_stamps.py).  __graft_entry__.build() asks for them, as the GPU
     tests load the redo build."""
-    srcs = [os.path.join(CSRC, f) for f in SRCS]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("td_kernels.h", "td_tables.h")] + [os.path.join(INC, "turbo_mi355x.h"),
-                                                                                       __file__]
+    # the sources and every kernel file, header and textual include of csrc: an edit to any of them rebuilds
+    deps = [os.path.join(CSRC, f) for f in SRCS]
+    deps += [p for pat in ("*.hip", "*.h", "*.hpp", "*.inc") for p in glob.glob(os.path.join(CSRC, pat))]
+    deps += [os.path.join(INC, "turbo_mi355x.h"), __file__]
     stamps = os.path.join(PKG, "libturbo_mi355x_stamps.so")   # diagnostic build (phase cycle stamps)
     redo = os.path.join(PKG, "libturbo_mi355x_redo.so")       # test build: every log-MAP alpha window takes
     comp, links = [], []                                       # the speculation's exact redo (test_gpu_decode)

@@ -663,17 +663,14 @@ __device__ __forceinline__ void tm_dma(Smem<T>& sm, int slot, const T* tmstore, 
 }
 
 // staged tempmax of window t -> its LDS slot (beta input; Max-Log-MAP's B-pass loader).  Batched
-// reads (TD_TM_CONVERT_BATCH, fp64): config 3 2380-2389 -> 2399-2404 Mbit/s (+0.8 %, 3 rounds); fp32
+// reads in fp64: config 3 2380-2389 -> 2399-2404 Mbit/s (+0.8 %, 3 rounds, against the masked form); fp32
 // Max-Log-MAP lost 1.3 % with it and keeps the masked form (profiles/r06/ab_maxlog_tm_convert.txt)
-#ifndef TD_TM_CONVERT_BATCH
-#define TD_TM_CONVERT_BATCH 1
-#endif
 template <typename T>
 __device__ __forceinline__ void tm_convert(Smem<T>& sm, int slot, int t, int lane)
 {
     const T* sv = reinterpret_cast<const T*>(&sm.stage[3][slot * kTmStageBytes<T>]);
     T* d = &sm.tm[t & 1][0][0];
-    if constexpr (TD_TM_CONVERT_BATCH != 0 && kW == 15 && sizeof(T) == 8) {
+    if constexpr (kW == 15 && sizeof(T) == 8) {
         // both reads before the first write and no lane masked (as tile_convert): lanes past the window
         // repeat its last element, the same value to the same address.  (The 12-step build is left as
         // it was: with this form its TU hits an instruction-selection error in the compiler.)
@@ -1125,11 +1122,8 @@ __device__ __forceinline__ void astore_row(T* sa, unsigned voff, T v)
 // 32768 shard level; the fp32 four-per-CU kernel of the 12-step TU lost 3.4 %, so it keeps the
 // committed order.  (With the flag left to the compiler, and with SLP packing the two buckets into
 // 16-bit pairs, the same speculation measured 1.2 % slower.)
-#ifndef TD_ASPEC
-#define TD_ASPEC (TD_KW == 15)
-#endif
 template <typename T, int ALGO>
-constexpr bool kASpec = ALGO == 0 && TD_ASPEC != 0;
+constexpr bool kASpec = ALGO == 0 && kW == 15;
 
 template <typename T, int ALGO, int K>
 struct AlphaSchedS {
@@ -1510,11 +1504,9 @@ __device__ __forceinline__ void fold_item(const Smem<T>& sm, const T* lut, int t
 // once per SISO, the window enters only as its ring slots (s3 = t % 3, s4 = t % kAvSlots, s2 = t &
 // 1, kept as running counters by the caller) and its first step i0.  Extrinsic written permuted
 // (ext_mode 2 / 3), no raw-LLR or Le dump (those take fold_item).
-// the folds' extrinsic stores non-temporal (A/B switch; read a SISO later by the loader's tile DMA):
-// config 2 level (1514-1516 against 1516-1522 Mbit/s, profiles/r06/ab_extrinsic_nt.txt), not kept
-#ifndef TD_EXT_NT
-#define TD_EXT_NT 0
-#endif
+// (The folds' extrinsic stores, read a SISO later by the loader's tile DMA, measured with
+// __builtin_nontemporal_store: config 2 level, 1514-1516 against 1516-1522 Mbit/s,
+// profiles/r06/ab_extrinsic_nt.txt; not kept.)
 template <typename T>
 struct FoldLane {
     int k, c;
@@ -1577,12 +1569,7 @@ __device__ __forceinline__ void fold_item_fast(const FoldLane<T>& fl, const T* l
     const T llr = r1 - r0;
     const T le = llr - la - (T)2 * ys;
     const int i = i0 + k;
-    if (i < ext_len) {
-        if constexpr (TD_EXT_NT != 0)
-            __builtin_nontemporal_store(le, &fl.ext[(size_t)wperm * kCw]);
-        else
-            fl.ext[(size_t)wperm * kCw] = le;
-    }
+    if (i < ext_len) fl.ext[(size_t)wperm * kCw] = le;
     if (fl.bits && i < K) fl.bits[wbit] = (llr < (T)0) ? 0 : 1;   // :862-879 at pi[i] (:1264)
 }
 
@@ -1601,19 +1588,13 @@ __device__ __forceinline__ void fold_item_fast(const FoldLane<T>& fl, const T* l
 // past the last window (kFSkip), so no F-pass DMA is in flight when F1 starts staging.
 template <int ALGO>
 constexpr int kBLoaderWave = ALGO == 1 ? 3 : 2;
-// Max-Log-MAP fold items sorted by recompute depth over the two fold waves (15-step windows; A/B
-// switch TD_ML_DEPTH) and its full windows through fold_item_fast (TD_ML_FAST)
-#ifndef TD_ML_DEPTH
-#define TD_ML_DEPTH 1
-#endif
-#ifndef TD_ML_FAST
-#define TD_ML_FAST 1
-#endif
+// Max-Log-MAP fold items sorted by recompute depth over the two fold waves (15-step windows).
+// Measured with the split and with the Max-Log-MAP full windows through fold_item_fast (as log-MAP's;
+// before, they took fold_item) each switched off: config 3 +0.6 % for the split, +3.4 % for the fast
+// path, +3.8 % together (profiles/r06/ab_maxlog_fold_fast.txt); both kept.
 template <typename T, int ALGO>
-constexpr bool kMlDepthSplit = TD_ML_DEPTH && ALGO == 1 && kCkPh<ALGO> == 1 && kW == 15 &&
+constexpr bool kMlDepthSplit = ALGO == 1 && kCkPh<ALGO> == 1 && kW == 15 &&
                                kFoldAOf<T, ALGO> == 64 && kTile - kTile / 3 > kLanes;
-template <typename T, int ALGO>
-constexpr bool kMlFast = TD_ML_FAST && ALGO == 1;
 template <int ALGO>
 constexpr bool kFSkip = kBLoaderWave<ALGO> == 3;   // (on its own, with F0 loading both passes: level)
 constexpr int kAlphaPrio = 2;   // VALU priority of the alpha wave in the F pass
@@ -2012,7 +1993,7 @@ __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& ds
             nfold = wave == 0 ? 64 : 56;
         }
         int j0 = 0;
-        if ((ALGO == 0 || kMlFast<T, ALGO>) && !dst.llr && !dst.le_dump && dst.ext_mode >= 2 && tl >= 1) {
+        if (!dst.llr && !dst.le_dump && dst.ext_mode >= 2 && tl >= 1) {   // both algorithms (fold_item_fast)
             // iterations 0, 1 fold nothing, 2 folds the last window (maybe partial): generic below;
             // here iterations 3 .. nB-1, i.e. the full windows wf = tl-1 .. 0
             for (int j = 0; j < 3; ++j) {
@@ -2259,13 +2240,8 @@ __global__ __launch_bounds__(kWaves * 64, 3) void turbo_decode_kernel3(DecodePar
 template <typename T, int ALGO>
 constexpr bool kOcc4 = 4 * (sizeof(Smem<T>) + 64) <= 160 * 1024 && kRoleRemat<T>;
 // fp32 four per CU from the 12-step-window build when this one's Smem does not fit four (launch_turbo4_w12)
-#ifdef TD_W12_TU
-template <typename T, int ALGO>
-constexpr bool kOcc4W12 = false;
-#else
 template <typename T, int ALGO>
 constexpr bool kOcc4W12 = !kOcc4<T, ALGO> && sizeof(T) == 4 && kW != 12;
-#endif
 template <typename T, int ALGO>
 __global__ __launch_bounds__(kWaves * 64, 4) void turbo_decode_kernel4(DecodeParams<T> p)
 {
@@ -2478,28 +2454,27 @@ __device__ __forceinline__ T sw_mstar(T x, T y, const char* lut)
 // 8-codeword groups; sw_demux_kernel writes this layout.)  Round 4 read the 8-codeword layout: eight
 // 64-byte pieces per wave load, half a cache line each.
 constexpr int kSwCw = 64;
-// cache policy of the windowed kernels' streams (TD_SW_NT bits): 1 checkpoint stores nt, 2 the beta
-// kernel's checkpoint DMA sc0 sc1 nt, 4 its input DMA sc0 sc1 nt, 8 the alpha kernel's input loads nt,
-// 16 the beta kernel's extrinsic stores nt.
-// The checkpoints are written once and read once, a launch later: kept out of L2 / MALL (3) config 5
-// runs 3410-3415 against 3335-3343 Mbit/s (+2.2 %, one box, 2 interleaved rounds); the inputs, which
-// both kernels read, lose with nt (7: level, 15: -0.5 %; profiles/r06/ab_window_cache_policy.txt); the
-// extrinsic stores with nt (19) another +1.6 % (3208-3210 against 3157-3160, profiles/r06/ab_extrinsic_nt.txt)
-#ifndef TD_SW_NT
-#define TD_SW_NT 19
-#endif
+// Cache policy of the windowed kernels' streams.  The checkpoints are written once and read once, a
+// launch later: kept out of L2 / MALL (stores nt, the beta kernel's checkpoint DMA sc0 sc1 nt) config 5
+// runs 3410-3415 against 3335-3343 Mbit/s (+2.2 %, one box, 2 interleaved rounds); the beta kernel's
+// extrinsic stores with nt another +1.6 % (3208-3210 against 3157-3160, profiles/r06/ab_extrinsic_nt.txt).
+// The inputs, which both kernels read, stay plain: measured with the beta kernel's input DMA at sc0 sc1
+// nt (level) and with the alpha kernel's input loads nt as well (-0.5 %), not kept
+// (profiles/r06/ab_window_cache_policy.txt).
+constexpr bool kSwCkStoreNt = true;   // sw_alpha_kernel's checkpoint stores nt
+constexpr bool kSwCkDmaNt = true;     // the beta kernel's checkpoint DMA sc0 sc1 nt (dma16_stream)
+constexpr bool kSwExtNt = true;       // the beta kernel's extrinsic stores nt
 template <typename T>
 __device__ __forceinline__ void sw_ck_store(T* p, T v)
 {
-    if constexpr ((TD_SW_NT & 1) != 0)
+    if constexpr (kSwCkStoreNt)
         __builtin_nontemporal_store(v, p);
     else
         *p = v;
 }
-template <int BIT>
-__device__ __forceinline__ void sw_dma(unsigned lds, const void* src)
+__device__ __forceinline__ void sw_ck_dma(unsigned lds, const void* src)
 {
-    if constexpr ((TD_SW_NT & BIT) != 0)
+    if constexpr (kSwCkDmaNt)
         dma16_stream(lds, src);
     else
         dma16(lds, src);
@@ -2515,15 +2490,9 @@ __device__ __forceinline__ SwRaw<T> sw_raw(const DecodeParams<T>& p, const WinAr
     const int ic = min(max(i, 0), p.L - 1);
     const size_t row = (size_t)cwv * p.L + ic, rowk = (size_t)cwv * p.K + min(ic, p.K - 1);
     SwRaw<T> r;
-    if constexpr ((TD_SW_NT & 8) != 0) {
-        r.ys = __builtin_nontemporal_load(&(dec ? p.sys2 : p.sys1)[row * kSwCw + lane]);
-        r.yp = __builtin_nontemporal_load(&(dec ? p.par2 : p.par1)[row * kSwCw + lane]);
-        r.la = __builtin_nontemporal_load(&a.la[dec][rowk * kSwCw + lane]);
-    } else {
-        r.ys = (dec ? p.sys2 : p.sys1)[row * kSwCw + lane];
-        r.yp = (dec ? p.par2 : p.par1)[row * kSwCw + lane];
-        r.la = a.la[dec][rowk * kSwCw + lane];
-    }
+    r.ys = (dec ? p.sys2 : p.sys1)[row * kSwCw + lane];
+    r.yp = (dec ? p.par2 : p.par1)[row * kSwCw + lane];
+    r.la = a.la[dec][rowk * kSwCw + lane];
     return r;
 }
 // the step's P, Q (see "gamma") with La zero where no extrinsic exists (la_ok: i < la_len)
@@ -2615,13 +2584,7 @@ __device__ __forceinline__ void sw_beta_step2(T (&b)[8], T (&c)[8], const SwIn<T
 // A scheduling fence between the positions of a fast segment: without it the scheduler hoists the
 // next position's table reads into the current one and the beta kernel needs 298 VGPRs (one wave per
 // SIMD); with it a position's live set is the per-position path's.
-#ifndef TD_SW_FENCE
-#define TD_SW_FENCE 1
-#endif
-__device__ __forceinline__ void sw_fence()
-{
-    if constexpr (TD_SW_FENCE) __builtin_amdgcn_sched_barrier(0);
-}
+__device__ __forceinline__ void sw_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 // LLR of step i (log_map.cpp:1024-1039): the two left folds of E over the 8 next states
 template <typename T, int ALGO>
@@ -2704,17 +2667,10 @@ __device__ __forceinline__ T* sw_ck(const WinArgs<T>& a, const SwTask& t, int s,
 }
 
 // ---- alpha: forward over the run, checkpoints every S positions of each sub-block
-// (s_setprio 2 on the alpha waves, to issue ahead of a co-resident beta wave, measured level: not kept)
-#ifndef TD_SW_ALPHA_WAVES
-#define TD_SW_ALPHA_WAVES 0
-#endif
-#if TD_SW_ALPHA_WAVES
-#define TD_SW_ALPHA_ATTR __attribute__((amdgpu_waves_per_eu(TD_SW_ALPHA_WAVES)))
-#else
-#define TD_SW_ALPHA_ATTR
-#endif
+// (s_setprio 2 on the alpha waves, to issue ahead of a co-resident beta wave, measured level: not kept;
+// an amdgpu_waves_per_eu hint on this kernel and on sw_beta_kernel, measured: not kept)
 template <typename T, int ALGO, int S>
-__global__ __launch_bounds__(256) TD_SW_ALPHA_ATTR void sw_alpha_kernel(DecodeParams<T> p, WinArgs<T> a)
+__global__ __launch_bounds__(256) void sw_alpha_kernel(DecodeParams<T> p, WinArgs<T> a)
 {
     __shared__ alignas(16) char lut_s[sw_lut_bytes<T, ALGO>()];
     if constexpr (ALGO != 1) sw_lut_fill<T, ALGO>(lut_s, p);
@@ -3085,20 +3041,12 @@ __global__ __launch_bounds__(256) void sw_alpha_lps_kernel(DecodeParams<T> p, Wi
 }
 
 // ---- beta + LLR: backward over the run in segments of S positions
-#ifndef TD_SW_BETA_WAVES
-#define TD_SW_BETA_WAVES 0
-#endif
-#if TD_SW_BETA_WAVES
-#define TD_SW_BETA_ATTR __attribute__((amdgpu_waves_per_eu(TD_SW_BETA_WAVES)))
-#else
-#define TD_SW_BETA_ATTR
-#endif
 // LF (lane folds; a batch of one codeword, the drop-in's frame): every lane of the wave runs codeword
 // 0's chains, and the S LLRs of a segment are folded side by side, position m in lane m, once the
 // segment's beta steps are done -- one fold latency a segment instead of S (the folds are the beta
 // kernel's longest dependent chains: 2 x 7 table max* a position).  Same operations, same order.
 template <typename T, int ALGO, int S, bool LF>
-__global__ __launch_bounds__(256) TD_SW_BETA_ATTR void sw_beta_kernel(DecodeParams<T> p, WinArgs<T> a, const int* __restrict__ pi,
+__global__ __launch_bounds__(256) void sw_beta_kernel(DecodeParams<T> p, WinArgs<T> a, const int* __restrict__ pi,
                                                       const int* __restrict__ pinv)
 {
     __shared__ alignas(16) char lut_s[sw_lut_bytes<T, ALGO>()];
@@ -3205,7 +3153,7 @@ __global__ __launch_bounds__(256) TD_SW_BETA_ATTR void sw_beta_kernel(DecodePara
             constexpr int kDma = 8 * 64 * (int)sizeof(T) / 1024;
 #pragma unroll
             for (int q = 0; q < kDma; ++q)
-                if constexpr (!kDiag<kDiagSwNoCk>) sw_dma<2>(ckslot_lds + q * 1024, src + q * 1024);
+                if constexpr (!kDiag<kDiagSwNoCk>) sw_ck_dma(ckslot_lds + q * 1024, src + q * 1024);
         }
         const size_t row = (size_t)cwv * L + nbp, rowk = (size_t)cwv * K + nbp;
         const char* src0 = reinterpret_cast<const char*>((dec ? p.sys2 : p.sys1) + row * kSwCw) + lane * 16;
@@ -3213,9 +3161,9 @@ __global__ __launch_bounds__(256) TD_SW_BETA_ATTR void sw_beta_kernel(DecodePara
         const char* src2 = reinterpret_cast<const char*>(a.la[dec] + rowk * kSwCw) + lane * 16;
 #pragma unroll
         for (int q = 0; q < kInDma; ++q) {
-            sw_dma<4>(inslot_lds + q * 1024, src0 + q * 1024);
-            sw_dma<4>(inslot_lds + S * kRowBytes + q * 1024, src1 + q * 1024);
-            sw_dma<4>(inslot_lds + 2 * S * kRowBytes + q * 1024, src2 + q * 1024);
+            dma16(inslot_lds + q * 1024, src0 + q * 1024);
+            dma16(inslot_lds + S * kRowBytes + q * 1024, src1 + q * 1024);
+            dma16(inslot_lds + 2 * S * kRowBytes + q * 1024, src2 + q * 1024);
         }
     };
     prefetch(bp);
@@ -3240,7 +3188,7 @@ __global__ __launch_bounds__(256) TD_SW_BETA_ATTR void sw_beta_kernel(DecodePara
 #pragma unroll
             for (int m = 0; m < S; ++m)
                 if (dst[m] && t.live) {
-                    if constexpr ((TD_SW_NT & 16) != 0)
+                    if constexpr (kSwExtNt)
                         __builtin_nontemporal_store(dlev[m], &le[(size_t)dpm[m] * kSwCw + lane]);
                     else
                         le[(size_t)dpm[m] * kSwCw + lane] = dlev[m];
@@ -3461,14 +3409,12 @@ __global__ __launch_bounds__(256) void bits_transpose_kernel(const uint8_t* __re
 }
 
 // checkpoint spacing S: the segment's alpha stays in registers.  fp64: 4 (round 4: 2 measured -12 %,
-// 3 and 5 -6 %); fp32: 8.
-#ifndef TD_SW_SEG64
-#define TD_SW_SEG64 4
-#endif
+// 3 and 5 -6 %; round 6: 8 measured 28 % slower, profiles/r06/ab_window_ckpt_spacing8.txt); fp32: 8.
+constexpr int kSwSeg64 = 4;
 template <typename T>
 constexpr int sw_seg()
 {
-    return sizeof(T) == 4 ? 8 : TD_SW_SEG64;
+    return sizeof(T) == 4 ? 8 : kSwSeg64;
 }
 
 // sub-blocks per lane run: one (M = 1) while a launch has fewer than kSwRunWaves one-sub-block waves,
@@ -3479,10 +3425,7 @@ constexpr int sw_seg()
 // 7.8 %, and 2048 waves a SISO -- one round of the beta kernel's 2048 slots (2 waves a SIMD) over the
 // two halves.  Measured (round 5, same box, forced run lengths, now td_debug_window_layout): M = 6 2462, 8 2467, 12 2553, 20 2525
 // (1.25 rounds), 24 2628, 32 2236 (3/4 of the slots), 48 1559 Mbit/s.
-#ifndef TD_SW_RUN_WAVES
-#define TD_SW_RUN_WAVES 2048
-#endif
-constexpr int kSwRunWaves = TD_SW_RUN_WAVES;
+constexpr int kSwRunWaves = 2048;
 
 int window_run(int L, int W, int g, int B, int ndec, int S, int force)
 {
@@ -3501,10 +3444,7 @@ int window_run(int L, int W, int g, int B, int ndec, int S, int force)
 // other's beta.  Used when each half keeps at least kSwHalfWaves waves of 64 codewords and a second
 // stream is given (td_api.cpp); SISO2's decisions of every wanted iteration are transposed after the
 // join (all_iters decodes keep one stream: their per-iteration transposes would re-join the halves).
-#ifndef TD_SW_HALF_WAVES
-#define TD_SW_HALF_WAVES 64
-#endif
-constexpr int kSwHalfWaves = TD_SW_HALF_WAVES;
+constexpr int kSwHalfWaves = 64;
 
 template <typename T, int ALGO>
 hipError_t launch_window_algo(const DecodeParams<T>& p, const WindowParams& w, const WindowBufs<T>& wb, hipStream_t st,
