@@ -140,6 +140,51 @@ int td_set_window_maxstar(td_handle* h, int form);
  * decode after td_set_window + td_reserve allocates and creates nothing and may be captured. */
 int td_set_window(td_handle* h, const td_window_params* w);
 
+/*
+ * Per-codeword early termination of the exact schedule (an extension: the reference always runs all
+ * N_ITERATION).  Off by default; with it off every decode launches the kernels it always did.
+ * Iteration numbers below are 1-based counts; row(n) is the hard-decision row after n iterations,
+ * exactly as a full decode produces it (row n-1 of an all_iters decode).
+ *   TD_STOP_HDA  codeword b stops after the smallest n >= max(2, min_iters) with row(n) == row(n-1)
+ *                on all K bits (hard-decision aided rule); without such an n, at `iterations`.
+ *   TD_STOP_CRC  it stops after the smallest n >= max(1, min_iters) at which the CRC-24 remainder of
+ *                row(n) is zero: the K bits in natural order, first bit first, zero initial state, no
+ *                final XOR -- the LTE code-block CRC.  crc_poly holds the 24 low-order coefficients
+ *                of the generator: 0x800063 gCRC24B, 0x864CFB gCRC24A.  Needs K > 24.
+ * Both: iters_used[b] = n and the decoded bits of b are row(n).  A codeword's result does not depend
+ * on the codewords it shares a batch (or a workgroup's group of 8) with: a stopped codeword's
+ * outputs are frozen while its group's other codewords go on, and the workgroup ends once all of
+ * its codewords have stopped.  With all_iters, rows <= n equal the full decode's and rows
+ * n+1 .. iterations are copies of row(n) (the frozen-row convention: per-iteration error counts and
+ * the drop-in's flow_decoded rows stay meaningful).  d_le entries of iterations <= iters_used[b]
+ * equal the full decode's; later entries are unspecified.  min_iters in [1, iterations];
+ * min_iters == iterations reproduces the full decode, with every count = iterations.
+ * The windowed schedule (td_set_window) has no early termination: setting a rule on a windowed
+ * handle, or a window on a handle with a rule, is TD_EINVAL.
+ * td_set_early_stop(NULL or rule TD_STOP_NONE) turns it off.  TD_EINVAL: unknown rule, min_iters out
+ * of range, TD_STOP_CRC with crc_poly == 0 or K <= 24, a windowed handle.  The CRC rule's device
+ * table is built here, so a decode allocates nothing for the feature (td_reserve + capture holds).
+ */
+enum td_stop_rule { TD_STOP_NONE = 0, TD_STOP_HDA = 1, TD_STOP_CRC = 2 };
+typedef struct td_stop_params {
+    int rule;            /* enum td_stop_rule */
+    int min_iters;       /* no codeword stops before this many iterations */
+    uint32_t crc_poly;   /* TD_STOP_CRC: the generator's 24 low-order coefficients */
+} td_stop_params;
+int td_set_early_stop(td_handle* h, const td_stop_params* s);
+/* td_decode_device plus d_iters: nullable int32 [B], iterations used per codeword.  td_decode_device
+ * (and td_decode_host) on a handle with a rule set behave like these with a null count pointer; these
+ * on a handle without a rule behave like the plain entry points and fill the counts with
+ * `iterations`. */
+int td_decode_device_stop(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
+                          int32_t* d_iters, void* stream);
+int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le, int* iters_used);
+/* Host only (no GPU): the CRC-24 remainder of bits[0..K) (one bit per byte) as TD_STOP_CRC defines it,
+ * and the per-position table the kernel uses -- table[i] = the remainder of the row with only bit i
+ * set, so that the remainder of any row is the XOR of the entries of its set bits. */
+uint32_t td_crc24_host(const uint8_t* bits, int K, uint32_t poly);
+int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table /* [K] */);
+
 /* Kernel timing (measurement support): while enabled, hipEvents on the decode stream bracket
  * the demultiplex kernel and the turbo kernel of every td_decode_device call.
  * td_profile_read synchronises on them, returns the average durations (ms) over the

@@ -16,6 +16,8 @@ TD_ALGO_LOGMAP, TD_ALGO_MAXLOG = 0, 1
 TD_F64, TD_F32 = 0, 1
 TD_WMAXSTAR_FAST, TD_WMAXSTAR_EXACT = 0, 1
 TD_MAXSTAR_WINDOW_FAST = 2   # td_maxstar_host_* algo: the windowed one-read table
+TD_STOP_NONE, TD_STOP_HDA, TD_STOP_CRC = 0, 1, 2
+CRC24A, CRC24B = 0x864CFB, 0x800063   # the LTE generators' 24 low-order coefficients (td_stop_params.crc_poly)
 
 # every symbol include/turbo_mi355x.h declares (tests check the .so exports all of them)
 EXPORTS = (
@@ -25,7 +27,8 @@ EXPORTS = (
     "td_debug_stamp_slots", "td_synth_seed", "td_synth_frames", "td_count_errors", "td_rand_window", "td_synth_seek",
     "td_set_window", "td_synth_modulation", "td_modulate", "td_demodulate", "td_debug_placement",
     "td_debug_placement_rule", "td_clock_read", "td_window_steps", "td_debug_placement_cost", "td_debug_window_layout",
-    "td_debug_workspace_bytes", "td_set_window_maxstar",
+    "td_debug_workspace_bytes", "td_set_window_maxstar", "td_set_early_stop", "td_decode_device_stop",
+    "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes",
 )
 
 
@@ -39,6 +42,10 @@ class TdParams(C.Structure):
 class TdWindowParams(C.Structure):
     _fields_ = [("window", C.c_int), ("overlap", C.c_int), ("nii", C.c_int), ("concurrent", C.c_int),
                 ("ext_scale", C.c_double)]
+
+
+class TdStopParams(C.Structure):
+    _fields_ = [("rule", C.c_int), ("min_iters", C.c_int), ("crc_poly", C.c_uint32)]
 
 
 class TurboError(RuntimeError):
@@ -95,6 +102,13 @@ def lib() -> C.CDLL:
     L.td_synth_frames.argtypes = [P, C.c_double, I, P, P, P]
     L.td_count_errors.argtypes = [P, P, I, P, I, P, P]
     L.td_set_window.argtypes = [P, C.POINTER(TdWindowParams)]
+    if hasattr(L, "td_set_early_stop"):   # early termination (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_set_early_stop.argtypes = [P, C.POINTER(TdStopParams)]
+        L.td_decode_device_stop.argtypes = [P, P, I, P, I, P, P, P]
+        L.td_decode_host_stop.argtypes = [P, P, I, P, P, P]
+        L.td_crc24_host.argtypes = [P, I, C.c_uint32]
+        L.td_crc24_host.restype = C.c_uint32
+        L.td_crc24_syndromes.argtypes = [I, C.c_uint32, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -28,10 +28,15 @@ class BerPoint:
     bit_errors: list = field(default_factory=list)     # per iteration
     block_errors: list = field(default_factory=list)   # per iteration
     K: int = 0
+    iters_used: int = 0   # sum over the counted frames of the iterations each used (early termination)
 
     @property
     def ber(self):
         return [e / (self.frames * self.K) if self.frames else math.nan for e in self.bit_errors]
+
+    @property
+    def mean_iters(self):
+        return self.iters_used / self.frames if self.frames else math.nan
 
     @property
     def bler(self):
@@ -50,6 +55,7 @@ def ber_point(codec: TurboCodec, ebn0_db: float, max_frames: int, min_block_erro
     info = torch.empty((batch, codec.K), dtype=torch.uint8, device=dev)
     llr64 = torch.empty((batch, n), dtype=torch.float64, device=dev)
     bits = torch.empty((batch, iters, codec.K), dtype=torch.uint8, device=dev)
+    used = torch.empty((batch,), dtype=torch.int32, device=dev)
     pt = BerPoint(ebn0_db, 0, [0] * iters, [0] * iters, codec.K)
     start = _frame_position(codec)
     done = False
@@ -57,10 +63,15 @@ def ber_point(codec: TurboCodec, ebn0_db: float, max_frames: int, min_block_erro
         B = min(batch, max_frames - pt.frames)
         codec.synth(B, ebn0_db, info[:B], llr64[:B])
         x = llr64[:B] if codec.precision == "f64" else llr64[:B].float()
-        codec.decode(x, bits[:B], all_iters=True)
+        # (with early termination the rows after a frame's stop are copies of its stop row, so the
+        # per-iteration counts below need no change)
+        stopping = getattr(codec, "early_stop", None) is not None
+        codec.decode(x, bits[:B], all_iters=True, iters_out=used[:B] if stopping else None)
         err = codec.count_errors(bits[:B], info[:B]).cpu().numpy()
+        n_it = used[:B].cpu().numpy() if stopping else [iters] * B
         for b in range(B):   # main.cpp's frame loop, in order
             pt.frames += 1
+            pt.iters_used += int(n_it[b])
             for it in range(iters):
                 pt.bit_errors[it] += int(err[b, it])
                 pt.block_errors[it] += int(err[b, it] != 0)
@@ -90,7 +101,8 @@ def ber_sweep(codec: TurboCodec, ebn0_list, seed: int, max_frames: int, min_bloc
         pt = ber_point(codec, float(e), max_frames, min_block_errors, batch)
         points.append(pt)
         if log:
-            log(f"Eb/N0 {e:.2f} dB: frames {pt.frames}, BER {pt.ber[-1]:.3e}, BLER {pt.bler[-1]:.3e}")
+            log(f"Eb/N0 {e:.2f} dB: frames {pt.frames}, BER {pt.ber[-1]:.3e}, BLER {pt.bler[-1]:.3e}, "
+                f"mean iterations {pt.mean_iters:.2f}")
     return points
 
 
@@ -152,6 +164,10 @@ def main(argv=None):
     ap.add_argument("--reference-gpu", type=int, default=0, metavar="P",
                     help="the reference GPU decoder with P sub-blocks (turboDecoderBianJieZhi.cu): "
                          "Max-Log-MAP fp32, window K/P, NII, concurrent SISOs, extrinsic x0.77")
+    ap.add_argument("--early-stop", default="", choices=["", "hda", "crc"],
+                    help="per-codeword early termination of the exact schedule (td_set_early_stop); the "
+                         "generator's frames carry no CRC, so crc only stops on a chance remainder")
+    ap.add_argument("--min-iters", type=int, default=1, help="no frame stops before this many iterations")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     start, end, step = a.ebn0
@@ -166,11 +182,14 @@ def main(argv=None):
         c.synth_modulation(a.modulation)
         if a.window:
             c.set_window(a.window, a.overlap, a.ext_scale, nii=a.nii, concurrent=a.concurrent)
+        if a.early_stop:
+            c.set_early_stop(a.early_stop, min_iters=a.min_iters)
         res = ber_sweep(c, pts, a.seed, a.max_frames, a.min_block_errors, a.batch,
                         log=lambda s: print(s, file=sys.stderr, flush=True))
     for p in res:
         print(f"{p.ebn0_db:.2f} frames {p.frames} " +
-              " ".join(f"{be}:{bl}" for be, bl in zip(p.bit_errors, p.block_errors)))
+              " ".join(f"{be}:{bl}" for be, bl in zip(p.bit_errors, p.block_errors)) +
+              f" mean_iters {p.mean_iters:.3f}")
     if a.out:
         write_result_txt(a.out, res, a.K, start, step, end, modulation=a.modulation)
     return 0

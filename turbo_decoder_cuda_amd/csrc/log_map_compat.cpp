@@ -25,6 +25,13 @@
 //   TD_CONCURRENT=1 both SISOs at once (Jacobi); TD_EXT_SCALE=s extrinsic scale (default 1)
 //   TD_WINDOW_MAXSTAR=exact  log_map.cpp's E_algorithm in the windowed log-MAP schedule (default: the
 //                   one-read table, td_set_window_maxstar)
+// Opt-in early termination of the exact schedule (td_set_early_stop; off by default, so the unchanged
+// main.cpp gets the reference's bits):
+//   TD_EARLY_STOP=hda|crc   a frame stops iterating once its hard decisions repeat (hda) or their
+//                   CRC-24 is zero (crc); the flow_decoded rows after the stop are copies of the stop row
+//   TD_STOP_MIN_ITERS=n     no frame stops before n iterations (default 1)
+//   TD_STOP_CRC_POLY=0x...  the CRC generator's 24 low-order coefficients (default 0x800063, gCRC24B)
+// TD_EARLY_STOP together with TD_WINDOW is an error (the windowed schedule has no early termination).
 // A windowed schedule changes the arithmetic (sub-block boundaries): its results are gated by
 // the BER curve, not bit-exact.  Log_MAP_decoder always runs the exact SISO.
 #include <cstdio>
@@ -66,6 +73,21 @@ double env_double(const char* name, double dflt)
 void set_schedule(td_handle* h)
 {
     const int W = env_int("TD_WINDOW", 0);
+    const char* es = std::getenv("TD_EARLY_STOP");
+    if (es && *es) {
+        td_stop_params sp{};
+        sp.rule = std::strcmp(es, "hda") == 0 ? TD_STOP_HDA : std::strcmp(es, "crc") == 0 ? TD_STOP_CRC : -1;
+        sp.min_iters = env_int("TD_STOP_MIN_ITERS", 1);
+        const char* poly = std::getenv("TD_STOP_CRC_POLY");
+        sp.crc_poly = poly && *poly ? (uint32_t)std::strtoul(poly, nullptr, 0) : 0x800063u;
+        if (W != 0) {
+            std::printf("turbo_mi355x: TD_EARLY_STOP and TD_WINDOW are both set: the windowed schedule has no early "
+                        "termination\n");
+            std::exit(1);
+        }
+        const int rc = td_set_early_stop(h, &sp);
+        if (rc) die("td_set_early_stop (TD_EARLY_STOP / TD_STOP_MIN_ITERS / TD_STOP_CRC_POLY)", rc);
+    }
     if (W == 0) return;
     td_window_params w{};
     w.window = W;

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "td_crc.h"
 #include "td_kernels.h"
 
 #ifndef TD_SYS2_IN_TURBO
@@ -70,6 +71,8 @@ struct td_handle {
     uint8_t* d_hbits = nullptr;
     void* d_hle = nullptr;
     size_t hin_b = 0, hbits_b = 0, hle_b = 0;
+    int32_t* d_hiters = nullptr;   // td_decode_host_stop's per-codeword iteration counts
+    size_t hiters_b = 0;
     std::vector<uint8_t> h_hbits;
     void* d_ws = nullptr;   // decode workspace
     std::vector<float> place_ms;   // td_reserve's placement trials (ms of one probe iteration each)
@@ -103,6 +106,9 @@ struct td_handle {
     // issued on a stream other than the previous decode's first waits (on the device) for that
     // decode to finish with the workspace.  Decodes on one handle therefore never overlap; callers
     // that want concurrent decodes use one handle per stream.
+    // early termination (td_set_early_stop): rule 0 = off
+    td_stop_params stop{TD_STOP_NONE, 1, 0};
+    uint32_t* d_crc = nullptr;      // [K] CRC syndromes by natural bit position (td_crc.h), built by td_set_early_stop
     hipEvent_t ws_free = nullptr;   // recorded after the last decode's kernels
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
@@ -519,7 +525,7 @@ int ensure_wstr(td_handle* h)
 
 template <typename T>
 int decode_device_t(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
-                    hipStream_t st)
+                    int32_t* d_iters, hipStream_t st)
 {
     const int G = groups_for(B);
     int rc = ensure_ws(h, G);
@@ -582,10 +588,17 @@ int decode_device_t(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int
                                 : td::launch_demux<T>(dp, static_cast<const T*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
-    if (h->wp.window)
+    if (h->wp.window) {
         e = td::launch_window<T>(dp, h->wp, wb, st, h->wstr);   // streams made by td_set_window
-    else
+    } else if (h->stop.rule != TD_STOP_NONE) {
+        const td::StopParams sp{h->stop.rule, h->stop.min_iters, h->d_crc, d_iters};
+        e = td::launch_turbo<T>(dp, st, false, &sp);
+    } else {
         e = td::launch_turbo<T>(dp, st);
+    }
+    // no rule (td_set_early_stop and td_set_window exclude each other): every codeword took them all
+    if (e == hipSuccess && d_iters && h->stop.rule == TD_STOP_NONE)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
     if (e != hipSuccess) return hip_fail(e, h->wp.window ? "launch_window" : "launch_turbo");
     h->clk_valid = !capturing;
     if (ev) {
@@ -879,6 +892,8 @@ int td_destroy(td_handle* h)
     if (h->d_hin) (void)hipFree(h->d_hin);
     if (h->d_hbits) (void)hipFree(h->d_hbits);
     if (h->d_hle) (void)hipFree(h->d_hle);
+    if (h->d_hiters) (void)hipFree(h->d_hiters);
+    if (h->d_crc) (void)hipFree(h->d_crc);
     if (h->d_win) (void)hipFree(h->d_win);
     if (h->d_wws) (void)hipFree(h->d_wws);
     release_wstr(h->wstr);
@@ -898,14 +913,64 @@ int td_reserve(td_handle* h, int B)
     return ensure_wws(h, win_carve(h, B).total);   // the windowed schedule's buffers as well
 }
 
-int td_decode_device(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
-                     void* stream)
+int td_decode_device_stop(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
+                          int32_t* d_iters, void* stream)
 {
     if (!h || !d_llr || !d_bits || B < 1) return fail(TD_EINVAL, "td_decode_device: bad argument");
     TD_HIP(hipSetDevice(h->p.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h->p.precision == TD_F64) return decode_device_t<double>(h, d_llr, B, d_bits, all_iters, d_le, st);
-    return decode_device_t<float>(h, d_llr, B, d_bits, all_iters, d_le, st);
+    if (h->p.precision == TD_F64) return decode_device_t<double>(h, d_llr, B, d_bits, all_iters, d_le, d_iters, st);
+    return decode_device_t<float>(h, d_llr, B, d_bits, all_iters, d_le, d_iters, st);
+}
+
+int td_decode_device(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
+                     void* stream)
+{
+    return td_decode_device_stop(h, d_llr, B, d_bits, all_iters, d_le, nullptr, stream);
+}
+
+int td_set_early_stop(td_handle* h, const td_stop_params* s)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_early_stop: null handle");
+    if (!s || s->rule == TD_STOP_NONE) {
+        h->stop = td_stop_params{TD_STOP_NONE, 1, 0};
+        return TD_OK;
+    }
+    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_early_stop: unknown rule");
+    if (s->min_iters < 1 || s->min_iters > h->p.iterations)
+        return fail(TD_EINVAL, "td_set_early_stop: min_iters must be in [1, iterations]");
+    if (h->wp.window)
+        return fail(TD_EINVAL, "td_set_early_stop: the windowed schedule (td_set_window) has no early termination");
+    if (s->rule == TD_STOP_CRC) {
+        if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
+            return fail(TD_EINVAL, "td_set_early_stop: crc_poly must be the 24 low-order coefficients, non-zero");
+        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_early_stop: TD_STOP_CRC needs K > 24");
+        TD_HIP(hipSetDevice(h->p.device));
+        // the table lives on the device from here on: a decode allocates nothing for the rule
+        if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
+            h->d_crc = nullptr;
+            return fail(TD_ENOMEM, "td_set_early_stop: hipMalloc failed");
+        }
+        std::vector<uint32_t> tab((size_t)h->p.K);
+        td::crc24_syndromes(h->p.K, s->crc_poly, tab.data());
+        TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
+        TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    h->stop = *s;
+    return TD_OK;
+}
+
+uint32_t td_crc24_host(const uint8_t* bits, int K, uint32_t poly)
+{
+    if (!bits || K < 1) return 0;
+    return td::crc24_bits(bits, K, poly);
+}
+
+int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table)
+{
+    if (K < 1 || !table) return fail(TD_EINVAL, "td_crc24_syndromes: bad argument");
+    td::crc24_syndromes(K, poly, table);
+    return TD_OK;
 }
 
 int td_set_window(td_handle* h, const td_window_params* w)
@@ -916,6 +981,9 @@ int td_set_window(td_handle* h, const td_window_params* w)
         return TD_OK;
     }
     if (w->window < 3 || w->window > 10000) return fail(TD_EINVAL, "td_set_window: window must be 0 or in [3, 10000]");
+    if (h->stop.rule != TD_STOP_NONE)
+        return fail(TD_EINVAL, "td_set_window: the handle has an early-termination rule (td_set_early_stop), which the "
+                               "windowed schedule does not support");
     if (w->overlap < 0 || w->overlap > 3 * w->window)
         return fail(TD_EINVAL, "td_set_window: overlap must be in [0, 3*window]");
     if (!(w->ext_scale > 0.0) || !(w->ext_scale <= 4.0))
@@ -1048,6 +1116,11 @@ int td_debug_stamp_slots(void)
 
 int td_decode_host(td_handle* h, const void* llr, int B, int* out, void* le)
 {
+    return td_decode_host_stop(h, llr, B, out, le, nullptr);
+}
+
+int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le, int* iters_used)
+{
     if (!h || !llr || !out || B < 1) return fail(TD_EINVAL, "td_decode_host: bad argument");
     TD_HIP(hipSetDevice(h->p.device));
     const int K = h->p.K, L = K + td::kMemory, it = h->p.iterations;
@@ -1066,14 +1139,17 @@ int td_decode_host(td_handle* h, const void* llr, int B, int* out, void* le)
         return e;
     };
     if (grow(&h->d_hin, h->hin_b, in_b) != hipSuccess || grow(reinterpret_cast<void**>(&h->d_hbits), h->hbits_b, bits_b) != hipSuccess ||
-        (le && grow(&h->d_hle, h->hle_b, le_b) != hipSuccess))
+        (le && grow(&h->d_hle, h->hle_b, le_b) != hipSuccess) ||
+        (iters_used && grow(reinterpret_cast<void**>(&h->d_hiters), h->hiters_b, (size_t)B * sizeof(int32_t)) != hipSuccess))
         return fail(TD_ENOMEM, "td_decode_host: hipMalloc failed");
     TD_HIP(hipMemcpy(h->d_hin, llr, in_b, hipMemcpyHostToDevice));
-    const int rc = td_decode_device(h, h->d_hin, B, h->d_hbits, 1, le ? h->d_hle : nullptr, nullptr);
+    const int rc = td_decode_device_stop(h, h->d_hin, B, h->d_hbits, 1, le ? h->d_hle : nullptr,
+                                         iters_used ? h->d_hiters : nullptr, nullptr);
     if (rc) return rc;
     h->h_hbits.resize(bits_b);
     TD_HIP(hipMemcpy(h->h_hbits.data(), h->d_hbits, bits_b, hipMemcpyDeviceToHost));   // waits for the decode (null stream)
     if (le) TD_HIP(hipMemcpy(le, h->d_hle, le_b, hipMemcpyDeviceToHost));
+    if (iters_used) TD_HIP(hipMemcpy(iters_used, h->d_hiters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < bits_b; ++i) out[i] = h->h_hbits[i];
     return TD_OK;
 }

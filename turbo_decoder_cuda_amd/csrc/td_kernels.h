@@ -81,6 +81,15 @@ struct DecodeParams {
     const LaneTables* lane;     // device copy (dynamic per-lane indexing stays out of scratch)
 };
 
+// Early termination (td_set_early_stop): a second argument of the stopping kernels only
+// (turbo_decode_stop_kernel*), so that the default kernels and their argument block stay as they are.
+struct StopParams {
+    int rule;                   // 1 hard decisions repeat (HDA), 2 CRC-24 remainder zero
+    int min_iters;              // smallest iteration count (1-based) a codeword may stop after
+    const uint32_t* crc_tab;    // [K] CRC syndrome of each natural bit position (td_crc.h), rule 2
+    int* iters_out;             // nullable [B]: iterations used per codeword
+};
+
 // demultiplex + x0.5 of the stream into the batch-interleaved arrays
 template <typename T>
 hipError_t launch_demux(const DecodeParams<T>& p, const T* flow, hipStream_t st);
@@ -89,11 +98,12 @@ template <typename T>
 hipError_t launch_window_demux(const DecodeParams<T>& p, const T* flow, hipStream_t st);
 // the turbo iterations (one wave per 8 codewords)
 template <typename T>
-hipError_t launch_turbo(const DecodeParams<T>& p, hipStream_t st, bool probe = false);   // probe: td_reserve's placement probe symbol
+hipError_t launch_turbo(const DecodeParams<T>& p, hipStream_t st, bool probe = false,   // probe: td_reserve's placement probe symbol
+                        const StopParams* stop = nullptr);                                // stop: the stopping kernels
 // fp32 at four workgroups per CU, from td_kernels_w12.hip (td_kernels.hip built with 12-step windows,
 // whose fp32 LDS fits four per CU; the default 15-step windows fit three)
 template <typename T, int ALGO>
-hipError_t launch_turbo4_w12(const DecodeParams<T>& p, hipStream_t st);
+hipError_t launch_turbo4_w12(const DecodeParams<T>& p, hipStream_t st, const StopParams* stop = nullptr);
 
 // sliding-window mode (BASELINE config 5, td_set_window): sub-blocks of `window` steps
 struct WindowParams {

@@ -1436,9 +1436,60 @@ __device__ __forceinline__ void alpha_recompute(T (&a)[8], T P, T Q, const T* lu
 //   LLR = E_seq(temp1) - E_seq(temp0)
 // with gamma[p][.][u] = +-P or +-Q (see "gamma"; kTrellisQ) -- the same two roundings as the
 // reference's (gamma + alpha) + beta.  Both folds run in the same lane (independent chains).
-template <typename T, int ALGO>
+//
+// Early termination (td_set_early_stop; the stopping kernels, STOP = true, only): a fold lane's share
+// of the rule's evidence over one SISO2 pass, kept in a register and merged into the group's LDS
+// words once at the end of the pass (stop_merge).  HDA: whether any decision the lane wrote differs
+// from the previous row's byte (the byte it overwrites; with all_iters the one a row earlier).  CRC:
+// the XOR of the syndromes (td_crc.h) of the positions where it wrote a 1 -- the CRC is linear, so the
+// group's XOR is the row's remainder.  A codeword in `done` has stopped: its row is frozen.
+struct StopLane {
+    int rule;                  // 1 HDA, 2 CRC (StopParams::rule)
+    int has_prev;              // HDA: a previous row exists (not in the first iteration)
+    unsigned done;             // bit c: codeword c of the group has stopped (or lies past B)
+    unsigned acc;              // this pass: HDA changed flag / CRC syndrome XOR
+    long long prev_off;        // HDA: the previous row's byte relative to the byte written (0 or -K)
+    const uint32_t* crc_tab;   // [K]
+    unsigned* lds;             // the group's words: [0] HDA changed mask (bit c); [c] CRC remainder
+};
+__device__ __forceinline__ void stop_decision(StopLane* sl, uint8_t* q, int wbit, int bit)
+{
+    if (sl->rule == 1) {
+        if (sl->has_prev) sl->acc |= (unsigned)(q[sl->prev_off] != bit);
+    } else if (bit) {
+        sl->acc ^= sl->crc_tab[wbit];
+    }
+    *q = (uint8_t)bit;
+}
+// The same in two steps for the folds' fast path: the operand (the previous row's byte, or the
+// position's syndrome) is loaded when the window's positions are known, ahead of the fold's
+// arithmetic, so that the load's latency is not added to every window.
+__device__ __forceinline__ unsigned stop_operand(const StopLane* sl, const uint8_t* q, int wbit)
+{
+    if (sl->rule == 1) return sl->has_prev ? q[sl->prev_off] : 0u;
+    return sl->crc_tab[wbit];
+}
+__device__ __forceinline__ void stop_commit(StopLane* sl, uint8_t* q, unsigned operand, int bit)
+{
+    if (sl->rule == 1) {
+        if (sl->has_prev) sl->acc |= (unsigned)(operand != (unsigned)bit);
+    } else if (bit) {
+        sl->acc ^= operand;
+    }
+    *q = (uint8_t)bit;
+}
+__device__ __forceinline__ void stop_merge(const StopLane* sl, int c)
+{
+    if (!sl->acc) return;
+    if (sl->rule == 1)
+        atomicOr(&sl->lds[0], 1u << c);
+    else
+        atomicXor(&sl->lds[c], sl->acc);
+}
+
+template <typename T, int ALGO, bool STOP = false>
 __device__ __forceinline__ void fold_item(const Smem<T>& sm, const T* lut, int t, int e, const SisoDst<T>& dst,
-                                          const Geom& gm)
+                                          const Geom& gm, StopLane* sl = nullptr)
 {
     const int k = e >> 3, c = e & 7;
     const int i = t * kW + k;
@@ -1495,6 +1546,11 @@ __device__ __forceinline__ void fold_item(const Smem<T>& sm, const T* lut, int t
     }
     if (b_ < gm.B) {
         if (dst.le_dump) dst.le_dump[(size_t)b_ * dst.dump_stride + (size_t)dst.dump_slot * gm.L + i] = le;
+        if constexpr (STOP) {
+            if (dst.bits && i < gm.K && !((sl->done >> c) & 1))
+                stop_decision(sl, &dst.bits[(size_t)b_ * dst.bits_stride + (size_t)dst.bits_row * gm.K + wbit],
+                                    wbit, (llr < (T)0) ? 0 : 1);
+        } else
         if (dst.bits && i < gm.K)   // decision (:862-879: LLR < 0 -> 0, else 1) at pi[i] (:1264)
             dst.bits[(size_t)b_ * dst.bits_stride + (size_t)dst.bits_row * gm.K + wbit] = (llr < (T)0) ? 0 : 1;
     }
@@ -1520,15 +1576,19 @@ struct FoldLane {
     T* ext;          // this codeword's extrinsic row base
     uint8_t* bits;   // this codeword's decision row (nullptr: none)
 };
-template <typename T, int ALGO>
+template <typename T, int ALGO, bool STOP = false>
 __device__ __forceinline__ void fold_item_fast(const FoldLane<T>& fl, const T* lut, int s3, int s4, int s2, int i0,
-                                               int ext_len, int K)
+                                               int ext_len, int K, StopLane* sl = nullptr)
 {
     const int k = fl.k;
     const T* g = fl.G + s3 * (kW * kCw * 4);
     const T P = g[0], Q = g[1], ys = g[2], la = g[3];
     const int* wp = fl.Wp + s3 * (kW * 2);
     const int wperm = wp[0], wbit = wp[1];
+    [[maybe_unused]] unsigned seen = 0;
+    if constexpr (STOP) {   // (a stopped codeword's fl.bits is null)
+        if (fl.bits && i0 + k < K) seen = stop_operand(sl, fl.bits + wbit, wbit);
+    }
     T a[8], b[8], t0[8], t1[8];
     load_block<T>(fl.Bv + s2 * (kW * kLanes), k, b);
     load_block<T>(fl.Av + s4 * (kW * kLanes), kFoldRows<ALGO> ? k : fl.arot, a);
@@ -1570,6 +1630,9 @@ __device__ __forceinline__ void fold_item_fast(const FoldLane<T>& fl, const T* l
     const T le = llr - la - (T)2 * ys;
     const int i = i0 + k;
     if (i < ext_len) fl.ext[(size_t)wperm * kCw] = le;
+    if constexpr (STOP) {
+        if (fl.bits && i < K) stop_commit(sl, fl.bits + wbit, seen, (llr < (T)0) ? 0 : 1);
+    } else
     if (fl.bits && i < K) fl.bits[wbit] = (llr < (T)0) ? 0 : 1;   // :862-879 at pi[i] (:1264)
 }
 
@@ -1727,11 +1790,13 @@ __device__ void bpass_loader(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T
 // One SISO over the workgroup's 8 codewords.  Each role runs its own loops (so only that role's
 // state is live in its code); every role executes the same sequence of wg_sync_lds barriers:
 // 1 (F prologue) + nT (F iterations) + nB (B iterations).
-template <typename T, int ALGO>
+template <typename T, int ALGO, bool STOP = false>
 __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& dst, const Geom& gm, T* astore,
-                        T* tmstore, const LaneTables* lt, int wave, int lane, unsigned long long* st)
+                        T* tmstore, const LaneTables* lt, int wave, int lane, unsigned long long* st,
+                        StopLane* sl = nullptr)
 {
     (void)st;
+    (void)sl;
     if constexpr (kRoleRemat<T>) touch(lane);   // nothing derived from the lane index is SISO-invariant (role remat)
     TD_STAMP(p0);
     const int nT = gm.nT;
@@ -2000,7 +2065,7 @@ __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& ds
                 TD_STAMP(b0);
                 const int wf = tl - j + 2;
                 if (lane < nfold && wf <= tl && (fe >> 3) < window_len(gm, wf))
-                    fold_item<T, ALGO>(sm, lut_col(sm, lane), wf, fe, dst, gm);
+                    fold_item<T, ALGO, STOP>(sm, lut_col(sm, lane), wf, fe, dst, gm, sl);
                 TD_STAMP(b1);
                 wg_sync_lds();
                 TD_STAMP(b2);
@@ -2028,12 +2093,15 @@ __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& ds
             const int b_ = gm.g * kCw + fl.c;
             fl.bits = (dst.bits && b_ < gm.B) ? dst.bits + (size_t)b_ * dst.bits_stride + (size_t)dst.bits_row * gm.K
                                               : nullptr;
+            if constexpr (STOP) {
+                if ((sl->done >> fl.c) & 1) fl.bits = nullptr;   // stopped: the row is frozen
+            }
             const T* lut = lut_col(sm, lane);
             int wf = tl - 1, s3 = wf % 3, s4 = wf % kAvSlots, s2 = wf & 1;
             for (int j = 3; j < nB; ++j, --wf) {
                 TD_STAMP(b0);
                 if (!kDiag<kDiagNoFold> && lane < nfold)
-                    fold_item_fast<T, ALGO>(fl, lut, s3, s4, s2, wf * kW, dst.ext_len, gm.K);
+                    fold_item_fast<T, ALGO, STOP>(fl, lut, s3, s4, s2, wf * kW, dst.ext_len, gm.K, sl);
                 s3 = s3 == 0 ? 2 : s3 - 1;
                 s4 = s4 == 0 ? kAvSlots - 1 : s4 - 1;
                 s2 ^= 1;
@@ -2049,12 +2117,15 @@ __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& ds
             TD_STAMP(b0);
             const int wf = tl - j + 2;
             if (!kDiag<kDiagNoFold> && lane < nfold && wf >= 0 && wf <= tl && (fe >> 3) < window_len(gm, wf))
-                fold_item<T, ALGO>(sm, lut_col(sm, lane), wf, fe, dst, gm);
+                fold_item<T, ALGO, STOP>(sm, lut_col(sm, lane), wf, fe, dst, gm, sl);
             TD_STAMP(b1);
             wg_sync_lds();
             TD_STAMP(b2);
             TD_ACC(2, b0, b1);
             TD_ACC(3, b1, b2);
+        }
+        if constexpr (STOP) {
+            if (dst.bits) stop_merge(sl, fe & 7);   // read by every wave after the SISO's end barrier
         }
     }
 }
@@ -2150,14 +2221,40 @@ __device__ __forceinline__ void wg_release(const WgPos& w, unsigned* slots)
 }
 
 // The whole turbo decode of 8 codewords per workgroup (TurboDecoding, log_map.cpp:1146-1280).
-template <typename T, int ALGO>
-__device__ __forceinline__ void turbo_decode_body(const DecodeParams<T>& p)
+//
+// STOP (the turbo_decode_stop_kernel* symbols, launched when a rule is set by td_set_early_stop):
+// per-codeword early termination.  SISO2 writes its decisions in every iteration and its fold lanes
+// gather the rule's evidence (StopLane); after the barrier that ends the pass every wave reads the
+// group's LDS words and takes the same decision: a codeword that meets the rule is added to `done`
+// (its row is frozen from then on: its lanes go on computing, so that no codeword's result depends on
+// its neighbours') and its iteration count recorded, and the workgroup leaves the loop once `done`
+// covers the group.  On the way out it fills the later all_iters rows of each codeword with copies
+// of its stop row and writes the counts.  The default kernels (STOP = false) contain none of this.
+template <typename T, int ALGO, bool STOP = false>
+__device__ __forceinline__ void turbo_decode_body(const DecodeParams<T>& p, const StopParams* sp = nullptr)
 {
+    (void)sp;
     const WgPos w = wg_pos(p.role_cus, p.cu_slots);
     Smem<T>& sm = *smem<T>();
     const int wave = w.role, lane = w.lane;
     lut_to_lds(p, sm, wave * kLanes + lane);
     if (wave == 1) set_beta_prio<T, ALGO>();   // beta first; alpha raises itself in the F pass
+    [[maybe_unused]] StopLane sl{};
+    [[maybe_unused]] unsigned long long used = 0;   // byte c: iterations used by codeword c
+    [[maybe_unused]] int stop_first = 0;
+    if constexpr (STOP) {
+        __shared__ unsigned s_stop[kCw];   // 32 B beside wg_pos's 20: within the 64 B the occupancy bounds allow
+        if (threadIdx.x < kCw) s_stop[threadIdx.x] = 0;
+        sl.rule = sp->rule;
+        sl.crc_tab = sp->crc_tab;
+        sl.lds = s_stop;
+        sl.prev_off = p.all_iters ? -(long long)p.K : 0;
+        for (int c = 0; c < kCw; ++c) {
+            if (w.g * kCw + c >= p.B) sl.done |= 1u << c;   // past the batch: nothing to wait for
+            used |= (unsigned long long)p.iters << (8 * c);
+        }
+        stop_first = max(sp->rule == 1 ? 2 : 1, sp->min_iters);
+    }
     __syncthreads();
 
     Geom gm{p.K, p.L, p.nT, p.B, w.g, p.G, p.pi, p.pinv};
@@ -2177,7 +2274,7 @@ __device__ __forceinline__ void turbo_decode_body(const DecodeParams<T>& p)
     // SISO pass s = 2*it + dec
     for (int s = 0; s < 2 * p.iters; ++s) {
         const int it = s >> 1, dec = s & 1;
-        const bool want_bits = dec == 1 && (p.all_iters || it == p.iters - 1);
+        const bool want_bits = dec == 1 && (STOP || p.all_iters || it == p.iters - 1);
         // decoder 1: La = deinterleaved Le of decoder 2 (:1221), zero before the first
         //            iteration (:1212-1215); its Le is written interleaved (ext12[pinv[i]]),
         //            i.e. already as decoder 2's La (:1242).
@@ -2189,12 +2286,53 @@ __device__ __forceinline__ void turbo_decode_body(const DecodeParams<T>& p)
                        want_bits ? p.bits : nullptr, p.all_iters ? it : 0, p.all_iters ? p.iters * p.K : p.K,
                        s, p.iters * 2 * p.L, (s == 0 && p.sys2_in_turbo) ? p.sys2 : nullptr};
         TD_STAMP(s0);
-        siso_wg<T, ALGO>(sm, src, dst, gm, p.astore, p.tmstore, p.lane, wave, lane, st);
+        if constexpr (STOP) {
+            sl.acc = 0;
+            sl.has_prev = it > 0;
+        }
+        siso_wg<T, ALGO, STOP>(sm, src, dst, gm, p.astore, p.tmstore, p.lane, wave, lane, st, &sl);
         TD_STAMP(s1);
         __syncthreads();   // extrinsic stores of this SISO visible to the next one's loads
         TD_STAMP(s2);
         TD_ACC(9, s0, s1);
         TD_ACC(10, s1, s2);
+        if constexpr (STOP) {
+            if (dec == 1 && it + 1 < p.iters) {   // (after the last iteration everything stops anyway)
+                // every wave reads the same words after the same barrier: the decision is workgroup-uniform
+                unsigned stop = 0;
+                if (it + 1 >= stop_first) {
+                    if (sl.rule == 1) {
+                        stop = ~sl.lds[0] & 0xffu;
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < kCw; ++c) stop |= (sl.lds[c] == 0 ? 1u : 0u) << c;
+                    }
+                }
+                stop = (unsigned)__builtin_amdgcn_readfirstlane((int)stop) & ~sl.done;
+#pragma unroll
+                for (int c = 0; c < kCw; ++c)
+                    if ((stop >> c) & 1)
+                        used = (used & ~(0xffull << (8 * c))) | ((unsigned long long)(it + 1) << (8 * c));
+                sl.done |= stop;
+                __syncthreads();   // all waves have read the words before they are cleared for the next pass
+                if (threadIdx.x < kCw) sl.lds[threadIdx.x] = 0;   // (the next merge is a whole SISO of barriers away)
+                if (sl.done == 0xffu) break;
+            }
+        }
+    }
+    if constexpr (STOP) {
+        // the loop's last barrier made the group's decision rows visible to all its waves
+        if (p.all_iters) {
+            for (int c = 0; c < kCw; ++c) {
+                const int b_ = w.g * kCw + c, n = (int)((used >> (8 * c)) & 0xff);
+                if (b_ >= p.B || n >= p.iters) continue;
+                uint8_t* row = p.bits + ((size_t)b_ * p.iters + (n - 1)) * p.K;   // row(n); rows n+1.. follow it
+                const int total = (p.iters - n) * p.K;
+                for (int e = (int)threadIdx.x; e < total; e += kWaves * kLanes) row[p.K + e] = row[e % p.K];
+            }
+        }
+        if (sp->iters_out && threadIdx.x < kCw && w.g * kCw + (int)threadIdx.x < p.B)
+            sp->iters_out[w.g * kCw + threadIdx.x] = (int)((used >> (8 * threadIdx.x)) & 0xff);
     }
     if (clk) {
         const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -2220,6 +2358,12 @@ __global__ __launch_bounds__(kWaves * 64, 2) void turbo_decode_kernel(DecodePara
 {
     turbo_decode_body<T, ALGO>(p);
 }
+// with early termination (td_set_early_stop)
+template <typename T, int ALGO>
+__global__ __launch_bounds__(kWaves * 64, 2) void turbo_decode_stop_kernel(DecodeParams<T> p, StopParams sp)
+{
+    turbo_decode_body<T, ALGO, true>(p, &sp);
+}
 
 // Large batches (more groups than two per CU): three workgroups per CU -- 24 codewords, 12 waves,
 // three per SIMD -- where the build fits them: at most 168 VGPRs without scratch (the build fails
@@ -2234,6 +2378,11 @@ __global__ __launch_bounds__(kWaves * 64, 3) void turbo_decode_kernel3(DecodePar
 {
     if constexpr (kOcc3<T, ALGO>) turbo_decode_body<T, ALGO>(p);
 }
+template <typename T, int ALGO>
+__global__ __launch_bounds__(kWaves * 64, 3) void turbo_decode_stop_kernel3(DecodeParams<T> p, StopParams sp)
+{
+    if constexpr (kOcc3<T, ALGO>) turbo_decode_body<T, ALGO, true>(p, &sp);
+}
 
 // More than three groups per CU: four workgroups per CU (16 waves, at most 128 VGPRs, a quarter of
 // the LDS) where they fit: fp32 with 12-step windows (36.7 KB of LDS, 67-79 VGPRs with role remat).
@@ -2246,6 +2395,11 @@ template <typename T, int ALGO>
 __global__ __launch_bounds__(kWaves * 64, 4) void turbo_decode_kernel4(DecodeParams<T> p)
 {
     if constexpr (kOcc4<T, ALGO>) turbo_decode_body<T, ALGO>(p);
+}
+template <typename T, int ALGO>
+__global__ __launch_bounds__(kWaves * 64, 4) void turbo_decode_stop_kernel4(DecodeParams<T> p, StopParams sp)
+{
+    if constexpr (kOcc4<T, ALGO>) turbo_decode_body<T, ALGO, true>(p, &sp);
 }
 
 // td_reserve's workspace-placement probe (td_api.cpp place_ws): the same code as
@@ -3689,16 +3843,16 @@ __global__ __launch_bounds__(256) void siso_out_kernel(DecodeParams<T> p, T* llr
 // Dynamic LDS above 64 KiB must be allowed per kernel (once per device and kernel).
 inline hipError_t allow_smem(const void* fn, size_t bytes)
 {
-    static thread_local const void* done_fn[32] = {};
-    static thread_local int done_dev[32] = {};
+    static thread_local const void* done_fn[64] = {};
+    static thread_local int done_dev[64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    for (int i = 0; i < 32; ++i)
+    for (int i = 0; i < 64; ++i)
         if (done_fn[i] == fn && done_dev[i] == dev) return hipSuccess;
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
-    for (int i = 0; i < 32; ++i)
+    for (int i = 0; i < 64; ++i)
         if (!done_fn[i]) {
             done_fn[i] = fn;
             done_dev[i] = dev;
@@ -3751,32 +3905,51 @@ int occupancy_pick(const DecodeParams<T>& p)
 }
 
 template <typename T, int ALGO>
-hipError_t launch_kernel4(const DecodeParams<T>& p, hipStream_t st)
+hipError_t launch_kernel4(const DecodeParams<T>& p, hipStream_t st, const StopParams* stop)
 {
-    hipError_t e = allow_smem(reinterpret_cast<const void*>(&turbo_decode_kernel4<T, ALGO>), sizeof(Smem<T>));
+    const void* k = stop ? reinterpret_cast<const void*>(&turbo_decode_stop_kernel4<T, ALGO>)
+                                : reinterpret_cast<const void*>(&turbo_decode_kernel4<T, ALGO>);
+    hipError_t e = allow_smem(k, sizeof(Smem<T>));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((turbo_decode_kernel4<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), sizeof(Smem<T>), st, p);
+    if (stop)
+        hipLaunchKernelGGL((turbo_decode_stop_kernel4<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), sizeof(Smem<T>), st, p,
+                           *stop);
+    else
+        hipLaunchKernelGGL((turbo_decode_kernel4<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), sizeof(Smem<T>), st, p);
     return hipGetLastError();
 }
 
 template <typename T, int ALGO>
-hipError_t launch_turbo_algo(const DecodeParams<T>& p, hipStream_t st, bool probe)
+hipError_t launch_turbo_algo(const DecodeParams<T>& p, hipStream_t st, bool probe, const StopParams* stop)
 {
     // the placement probe times the kernel the decode will run: at two per CU under its own symbol (the
     // traces list it apart); at three or four per CU (fp32 batches beyond one dispatch round) the
     // decode's own kernel3 / kernel4
     const int occ = occupancy_pick<T, ALGO>(p);
     if (occ == 4) {
-        if constexpr (kOcc4<T, ALGO>) return launch_kernel4<T, ALGO>(p, st);
+        if constexpr (kOcc4<T, ALGO>) return launch_kernel4<T, ALGO>(p, st, stop);
 #ifndef TD_W12_TU
-        else if constexpr (kOcc4W12<T, ALGO>) return launch_turbo4_w12<T, ALGO>(p, st);
+        else if constexpr (kOcc4W12<T, ALGO>) return launch_turbo4_w12<T, ALGO>(p, st, stop);
 #endif
         else return hipErrorInvalidConfiguration;
     }
     if (occ == 3) {
-        hipError_t e = allow_smem(reinterpret_cast<const void*>(&turbo_decode_kernel3<T, ALGO>), wg_lds3<T>());
+        const void* k3 = stop ? reinterpret_cast<const void*>(&turbo_decode_stop_kernel3<T, ALGO>)
+                                     : reinterpret_cast<const void*>(&turbo_decode_kernel3<T, ALGO>);
+        hipError_t e = allow_smem(k3, wg_lds3<T>());
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((turbo_decode_kernel3<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), wg_lds3<T>(), st, p);
+        if (stop)
+            hipLaunchKernelGGL((turbo_decode_stop_kernel3<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), wg_lds3<T>(), st, p,
+                               *stop);
+        else
+            hipLaunchKernelGGL((turbo_decode_kernel3<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), wg_lds3<T>(), st, p);
+        return hipGetLastError();
+    }
+    if (stop && !probe) {   // early termination at two per CU (the placement probe never stops early)
+        hipError_t e = allow_smem(reinterpret_cast<const void*>(&turbo_decode_stop_kernel<T, ALGO>), wg_lds<T>());
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((turbo_decode_stop_kernel<T, ALGO>), dim3(p.G), dim3(kWaves * kLanes), wg_lds<T>(), st, p,
+                           *stop);
         return hipGetLastError();
     }
     const void* k = probe ? reinterpret_cast<const void*>(&turbo_placement_probe_kernel<T, ALGO>)
@@ -3816,9 +3989,9 @@ hipError_t launch_demux(const DecodeParams<T>& p, const T* flow, hipStream_t st)
 }
 
 template <typename T>
-hipError_t launch_turbo(const DecodeParams<T>& p, hipStream_t st, bool probe)
+hipError_t launch_turbo(const DecodeParams<T>& p, hipStream_t st, bool probe, const StopParams* stop)
 {
-    return p.algo == 1 ? launch_turbo_algo<T, 1>(p, st, probe) : launch_turbo_algo<T, 0>(p, st, probe);
+    return p.algo == 1 ? launch_turbo_algo<T, 1>(p, st, probe, stop) : launch_turbo_algo<T, 0>(p, st, probe, stop);
 }
 
 template <typename T>
@@ -3839,8 +4012,8 @@ hipError_t launch_siso(const DecodeParams<T>& p, const T* recs, const T* la, T* 
 #if !defined(TD_W12_TU) && !defined(TD_WIN_TU)
 template hipError_t launch_demux<double>(const DecodeParams<double>&, const double*, hipStream_t);
 template hipError_t launch_demux<float>(const DecodeParams<float>&, const float*, hipStream_t);
-template hipError_t launch_turbo<double>(const DecodeParams<double>&, hipStream_t, bool);
-template hipError_t launch_turbo<float>(const DecodeParams<float>&, hipStream_t, bool);
+template hipError_t launch_turbo<double>(const DecodeParams<double>&, hipStream_t, bool, const StopParams*);
+template hipError_t launch_turbo<float>(const DecodeParams<float>&, hipStream_t, bool, const StopParams*);
 template hipError_t launch_siso<double>(const DecodeParams<double>&, const double*, const double*, double*, int,
                                         double*, hipStream_t);
 template hipError_t launch_siso<float>(const DecodeParams<float>&, const float*, const float*, float*, int, float*,
@@ -3862,14 +4035,14 @@ template hipError_t launch_window<float>(const DecodeParams<float>&, const Windo
 #ifdef TD_W12_TU
 namespace td {
 template <typename T, int ALGO>
-hipError_t launch_turbo4_w12(const DecodeParams<T>& p, hipStream_t st)
+hipError_t launch_turbo4_w12(const DecodeParams<T>& p, hipStream_t st, const StopParams* stop)
 {
     static_assert(td_w12::kOcc4<T, ALGO>, "the 12-step-window build has the four-per-CU kernel");
     DecodeParams<T> q = p;
     q.nT = (q.L + td_w12::kW - 1) / td_w12::kW;   // windows of this build
-    return td_w12::launch_kernel4<T, ALGO>(q, st);
+    return td_w12::launch_kernel4<T, ALGO>(q, st, stop);
 }
-template hipError_t launch_turbo4_w12<float, 0>(const DecodeParams<float>&, hipStream_t);
-template hipError_t launch_turbo4_w12<float, 1>(const DecodeParams<float>&, hipStream_t);
+template hipError_t launch_turbo4_w12<float, 0>(const DecodeParams<float>&, hipStream_t, const StopParams*);
+template hipError_t launch_turbo4_w12<float, 1>(const DecodeParams<float>&, hipStream_t, const StopParams*);
 }  // namespace td
 #endif

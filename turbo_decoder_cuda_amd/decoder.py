@@ -24,6 +24,7 @@ TERMINATED = 1     # log_map.h:24
 
 _ALGOS = {"logmap": N.TD_ALGO_LOGMAP, "maxlog": N.TD_ALGO_MAXLOG}
 _PRECS = {"f64": N.TD_F64, "f32": N.TD_F32}
+_STOP_RULES = {None: N.TD_STOP_NONE, "hda": N.TD_STOP_HDA, "crc": N.TD_STOP_CRC}
 
 
 def stream_length(K: int) -> int:
@@ -44,6 +45,7 @@ class TurboCodec:
         N.check(N.lib().td_create(C.byref(h), C.byref(p)))
         self._h = h
         self.device = int(device)
+        self.early_stop = None   # set_early_stop
 
     # -- lifetime (TurboCodingRelease) -------------------------------------------------
     def close(self) -> None:
@@ -105,33 +107,54 @@ class TurboCodec:
         N.check(N.lib().td_set_window(self._h, C.byref(w)))
         self.window = int(window)
 
+    def set_early_stop(self, rule=None, min_iters: int = 1, crc_poly: int = N.CRC24B) -> None:
+        """Per-codeword early termination of the exact schedule (td_set_early_stop): rule "hda" (a
+        codeword stops once its hard decisions repeat), "crc" (once their CRC-24 with `crc_poly` is
+        zero; gCRC24B by default) or None (off).  No codeword stops before `min_iters` iterations.
+        With all_iters the rows after a codeword's stop are copies of its stop row."""
+        if rule not in _STOP_RULES:
+            raise ValueError(f"rule must be 'hda', 'crc' or None, got {rule!r}")
+        s = N.TdStopParams(_STOP_RULES[rule], int(min_iters), int(crc_poly) & 0xFFFFFFFF)
+        N.check(N.lib().td_set_early_stop(self._h, C.byref(s)))
+        self.early_stop = rule
+
     def debug_window_layout(self, run: int = 0, run_a: int = 0, parts: int = 0) -> None:
         """Windowed kernels' layout for tests and measurements (td_debug_window_layout): sub-blocks
         per lane run (beta and alpha kernels) and batch parts; 0 = the layout's own choice."""
         N.check(N.lib().td_debug_window_layout(self._h, int(run), int(run_a), int(parts)))
 
     # -- TurboDecoding, host arrays ------------------------------------------------------
-    def TurboDecoding(self, flow: np.ndarray, return_le: bool = False):
+    def TurboDecoding(self, flow: np.ndarray, return_le: bool = False, return_iters: bool = False):
         """flow [B, 3K+12] (or one row) -> out int32 [B, iterations, K] (the reference's
-        flow_decoded rows); with return_le also Le [B, iterations, 2, K+3]."""
+        flow_decoded rows); with return_le also Le [B, iterations, 2, K+3]; with return_iters also
+        the iterations each codeword used, int32 [B] (all `iterations` unless set_early_stop)."""
         flow = np.ascontiguousarray(flow, dtype=self.dtype)
         one = flow.ndim == 1
         flow = flow.reshape(-1, stream_length(self.K))
         B = flow.shape[0]
         out = np.zeros((B, self.iterations, self.K), dtype=np.int32)
         le = np.zeros((B, self.iterations, 2, self.L), dtype=self.dtype) if return_le else None
-        N.check(N.lib().td_decode_host(self._h, flow.ctypes.data_as(C.c_void_p), B,
-                                       out.ctypes.data_as(C.c_void_p),
-                                       le.ctypes.data_as(C.c_void_p) if return_le else None))
+        used = np.zeros(B, dtype=np.int32) if return_iters else None
+        le_p = le.ctypes.data_as(C.c_void_p) if return_le else None
+        if return_iters:
+            N.check(N.lib().td_decode_host_stop(self._h, flow.ctypes.data_as(C.c_void_p), B,
+                                                out.ctypes.data_as(C.c_void_p), le_p, used.ctypes.data_as(C.c_void_p)))
+        else:
+            N.check(N.lib().td_decode_host(self._h, flow.ctypes.data_as(C.c_void_p), B,
+                                           out.ctypes.data_as(C.c_void_p), le_p))
         if one:
             out, le = out[0], (le[0] if return_le else None)
-        return (out, le) if return_le else out
+            used = int(used[0]) if return_iters else None
+        res = (out,) + ((le,) if return_le else ()) + ((used,) if return_iters else ())
+        return res if len(res) > 1 else out
 
     # -- device-resident decode (torch tensors as HBM buffers) ---------------------------
-    def decode(self, llr, bits=None, all_iters: bool = False, le=None, stream=None):
+    def decode(self, llr, bits=None, all_iters: bool = False, le=None, stream=None, iters_out=None):
         """llr: torch tensor [B, 3K+12] on this codec's device (float64 for f64, float32 for f32).
         Returns uint8 bits [B, K] (or [B, iterations, K] with all_iters).  Asynchronous on
-        `stream` (default: torch's current stream)."""
+        `stream` (default: torch's current stream).  iters_out: None, an int32 [B] tensor that
+        receives the iterations each codeword used, or True to have one made: the call then returns
+        (bits, iters_out)."""
         import torch
 
         want = torch.float64 if self.precision == "f64" else torch.float32
@@ -149,12 +172,22 @@ class TurboCodec:
             self._check_out("bits", bits, torch.uint8, shape, llr.device)
         if le is not None:
             self._check_out("le", le, want, (B, self.iterations, 2, self.L), llr.device)
+        made = iters_out is True
+        if made:
+            iters_out = torch.empty((B,), dtype=torch.int32, device=llr.device)
+        elif iters_out is not None:
+            self._check_out("iters_out", iters_out, torch.int32, (B,), llr.device)
         if stream is None:
             stream = torch.cuda.current_stream(llr.device)
-        N.check(N.lib().td_decode_device(self._h, C.c_void_p(llr.data_ptr()), B, C.c_void_p(bits.data_ptr()),
-                                         int(all_iters), C.c_void_p(le.data_ptr()) if le is not None else None,
-                                         C.c_void_p(stream.cuda_stream)))
-        return bits
+        le_p = C.c_void_p(le.data_ptr()) if le is not None else None
+        if iters_out is None:
+            N.check(N.lib().td_decode_device(self._h, C.c_void_p(llr.data_ptr()), B, C.c_void_p(bits.data_ptr()),
+                                             int(all_iters), le_p, C.c_void_p(stream.cuda_stream)))
+            return bits
+        N.check(N.lib().td_decode_device_stop(self._h, C.c_void_p(llr.data_ptr()), B, C.c_void_p(bits.data_ptr()),
+                                              int(all_iters), le_p, C.c_void_p(iters_out.data_ptr()),
+                                              C.c_void_p(stream.cuda_stream)))
+        return (bits, iters_out) if made else bits
 
     @staticmethod
     def _check_out(name, t, dtype, shape, device) -> None:
@@ -165,14 +198,20 @@ class TurboCodec:
                              f"got {t.dtype} {tuple(t.shape)} on {t.device}")
 
     def decode_raw(self, llr_ptr: int, B: int, bits_ptr: int, all_iters: bool = False, le_ptr: int = 0,
-                   stream_ptr: int = 0) -> None:
-        """td_decode_device on raw device pointers (no checks possible here: the caller owns the
-        sizes -- llr B*(3K+12), bits B*K or B*iterations*K bytes, le B*iterations*2*(K+3))."""
+                   stream_ptr: int = 0, iters_ptr: int = 0) -> None:
+        """td_decode_device (td_decode_device_stop with iters_ptr) on raw device pointers (no checks possible here: the caller owns the
+        sizes -- llr B*(3K+12), bits B*K or B*iterations*K bytes, le B*iterations*2*(K+3), iters B
+        int32 or null)."""
         if B < 0 or not llr_ptr or not bits_ptr:
             raise ValueError("decode_raw: B >= 0 and non-null llr / bits pointers")
-        N.check(N.lib().td_decode_device(self._h, C.c_void_p(llr_ptr), int(B), C.c_void_p(bits_ptr),
-                                         int(all_iters), C.c_void_p(le_ptr) if le_ptr else None,
-                                         C.c_void_p(stream_ptr) if stream_ptr else None))
+        if not iters_ptr:
+            N.check(N.lib().td_decode_device(self._h, C.c_void_p(llr_ptr), int(B), C.c_void_p(bits_ptr),
+                                             int(all_iters), C.c_void_p(le_ptr) if le_ptr else None,
+                                             C.c_void_p(stream_ptr) if stream_ptr else None))
+            return
+        N.check(N.lib().td_decode_device_stop(self._h, C.c_void_p(llr_ptr), int(B), C.c_void_p(bits_ptr),
+                                              int(all_iters), C.c_void_p(le_ptr) if le_ptr else None,
+                                              C.c_void_p(iters_ptr), C.c_void_p(stream_ptr) if stream_ptr else None))
 
     # -- measurement ---------------------------------------------------------------------
     def profile(self, on: bool = True) -> None:
