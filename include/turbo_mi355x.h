@@ -159,8 +159,8 @@ int td_set_window(td_handle* h, const td_window_params* w);
  * the drop-in's flow_decoded rows stay meaningful).  d_le entries of iterations <= iters_used[b]
  * equal the full decode's; later entries are unspecified.  min_iters in [1, iterations];
  * min_iters == iterations reproduces the full decode, with every count = iterations.
- * The windowed schedule (td_set_window) has no early termination: setting a rule on a windowed
- * handle, or a window on a handle with a rule, is TD_EINVAL.
+ * These entry points belong to the exact schedule: setting a rule on a windowed handle, or a window
+ * on a handle with a rule, is TD_EINVAL.  The windowed schedule's rule is td_set_window_stop (below).
  * td_set_early_stop(NULL or rule TD_STOP_NONE) turns it off.  TD_EINVAL: unknown rule, min_iters out
  * of range, TD_STOP_CRC with crc_poly == 0 or K <= 24, a windowed handle.  The CRC rule's device
  * table is built here, so a decode allocates nothing for the feature (td_reserve + capture holds).
@@ -172,10 +172,43 @@ typedef struct td_stop_params {
     uint32_t crc_poly;   /* TD_STOP_CRC: the generator's 24 low-order coefficients */
 } td_stop_params;
 int td_set_early_stop(td_handle* h, const td_stop_params* s);
+/*
+ * Per-codeword early termination of the windowed schedule: the same two rules, td_stop_params, frozen-row
+ * convention and iters_used output, judged on the windowed decode's own rows.  Off by default; with it
+ * off a windowed decode launches the kernels it always did.
+ *   row(n)  the hard-decision row after n iterations of the full windowed decode with the handle's
+ *           window parameters, max* form, precision and algorithm (row n-1 of an all_iters decode with
+ *           the rule off).
+ *   TD_STOP_HDA  codeword b stops after the smallest n >= max(2, min_iters) with row(n) == row(n-1) on
+ *                all K bits; without such an n, at `iterations`.
+ *   TD_STOP_CRC  after the smallest n >= max(1, min_iters) with CRC-24(row(n)) == 0 (the polynomial
+ *                convention of td_set_early_stop).  Needs K > 24.
+ * iters_used[b] = n and the decoded bits of b are row(n).  With all_iters, rows <= n equal the full
+ * decode's and rows n+1 .. iterations are copies of row(n).  d_le entries of iterations <= n equal the
+ * full decode's; later entries are unspecified.  A codeword's result does not depend on its batch
+ * companions: not on its wave of 64, its workgroup, its lane-run layout (td_debug_window_layout), nor
+ * on the batch parts and streams -- a stopped codeword's outputs are frozen while its wave's other
+ * codewords go on, and a wave ends its launches at once when all of its codewords have stopped (which
+ * is where the time is saved).  min_iters == iterations reproduces the full decode byte for byte.
+ * This holds for every schedule option: serial and concurrent SISOs, NII on and off, any ext_scale and
+ * overlap, both max* forms and Max-Log-MAP, fp64 and fp32, batches of one codeword.
+ * Valid only on a handle whose current schedule is windowed (td_set_window first): otherwise
+ * TD_EINVAL.  Argument checks as td_set_early_stop (TD_EINVAL: unknown rule, min_iters outside
+ * [1, iterations], TD_STOP_CRC with crc_poly == 0 or K <= 24); a failed call leaves the previous
+ * setting in place.  NULL or rule TD_STOP_NONE turns the rule off.  The rule survives later
+ * td_set_window calls with window > 0; td_set_window(NULL or window 0) clears it.  The CRC rule's
+ * device table is built here, and the rule's per-codeword state lives in the windowed buffers that
+ * td_reserve sizes (whether or not a rule is set), so after td_reserve a decode allocates and creates
+ * nothing and may be captured into a hipGraph.  td_decode_device_stop / td_decode_host_stop fill the
+ * counts; the plain entry points behave like them with a null count pointer.
+ * td_clock_read after a decode with this rule returns TD_EINVAL: the stopping kernels take no clock
+ * sample (the workgroup that takes it may have nothing left to do).
+ */
+int td_set_window_stop(td_handle* h, const td_stop_params* s);
 /* td_decode_device plus d_iters: nullable int32 [B], iterations used per codeword.  td_decode_device
  * (and td_decode_host) on a handle with a rule set behave like these with a null count pointer; these
- * on a handle without a rule behave like the plain entry points and fill the counts with
- * `iterations`. */
+ * on a handle without a rule (of either schedule) behave like the plain entry points and fill the
+ * counts with `iterations`. */
 int td_decode_device_stop(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le,
                           int32_t* d_iters, void* stream);
 int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le, int* iters_used);
@@ -197,7 +230,8 @@ int td_profile_read(td_handle* h, float* demux_ms, float* decode_ms, int* launch
  * last SISO2 beta launch (round 5).  td_clock_read waits for this handle's last decode (not the
  * whole device) and returns the sustained shader clock (GHz) over that workgroup's span (ms: the
  * whole launch for the exact schedule, one workgroup's lifetime for a windowed one);
- * TD_EINVAL before any decode or when the last decode was graph-captured. */
+ * TD_EINVAL before any decode, when the last decode was graph-captured, or when it was a windowed
+ * decode with early termination (td_set_window_stop). */
 int td_clock_read(td_handle* h, double* sclk_ghz, double* span_ms);
 
 /* Diagnostics: in a library built with -DTD_STAMPS (td_debug_stamp_slots() > 0) the turbo

@@ -5,13 +5,23 @@ the functions between the `-- Begin function` / `-- End function` markers, each 
 file and the lines that name the per-compile __hip_cuid_ symbol.
 
     compare_device_asm.py OLD.s NEW.s      exit 0 and "IDENTICAL n kernels, m functions" if equal
+    compare_device_asm.py --allow-new OLD.s NEW.s
+                                           NEW may hold further kernels and functions (a change that adds
+                                           variants under their own symbols); everything in OLD must be
+                                           in NEW, equal.  Labels carry the function's ordinal in the file
+                                           (.LBB12_3, .Lfunc_end12), which moves when functions are added:
+                                           the ordinal and the comments that repeat it are left out of the
+                                           comparison in this mode.
 """
 import re
 import sys
 
 
-def pieces(path):
+def pieces(path, strip_ordinals=False):
     text = "".join(l for l in open(path) if "__hip_cuid_" not in l)
+    if strip_ordinals:
+        text = re.sub(r"(\.LBB|\.Lfunc_end|\.Lfunc_begin|\bBB)\d+", r"\1", text)
+        text = re.sub(r"[ \t]+;", " ;", text)   # the comment column moves with the label's width
     out = {}
     for m in re.finditer(r"-- Begin function (\S+)\n(.*?)-- End function", text, re.S):
         out["fn " + m.group(1)] = m.group(2)
@@ -30,8 +40,10 @@ def pieces(path):
 
 
 def main():
-    old, new = pieces(sys.argv[1]), pieces(sys.argv[2])
-    bad = [k for k in sorted(set(old) | set(new)) if old.get(k) != new.get(k)]
+    args = [a for a in sys.argv[1:] if a != "--allow-new"]
+    allow_new = len(args) != len(sys.argv) - 1
+    old, new = pieces(args[0], allow_new), pieces(args[1], allow_new)
+    bad = [k for k in sorted(set(old) | set(new)) if old.get(k) != new.get(k) and not (allow_new and k not in old)]
     for k in bad:
         print(("DIFFERS " if k in old and k in new else "ONLY IN OLD " if k in old else "ONLY IN NEW ") + k)
     if not bad:

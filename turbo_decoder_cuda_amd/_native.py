@@ -28,7 +28,7 @@ EXPORTS = (
     "td_set_window", "td_synth_modulation", "td_modulate", "td_demodulate", "td_debug_placement",
     "td_debug_placement_rule", "td_clock_read", "td_window_steps", "td_debug_placement_cost", "td_debug_window_layout",
     "td_debug_workspace_bytes", "td_set_window_maxstar", "td_set_early_stop", "td_decode_device_stop",
-    "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes",
+    "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
 )
 
 
@@ -109,6 +109,8 @@ def lib() -> C.CDLL:
         L.td_crc24_host.argtypes = [P, I, C.c_uint32]
         L.td_crc24_host.restype = C.c_uint32
         L.td_crc24_syndromes.argtypes = [I, C.c_uint32, P]
+    if hasattr(L, "td_set_window_stop"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_set_window_stop.argtypes = [P, C.POINTER(TdStopParams)]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -167,6 +167,8 @@ def main(argv=None):
     ap.add_argument("--early-stop", default="", choices=["", "hda", "crc"],
                     help="per-codeword early termination of the exact schedule (td_set_early_stop); the "
                          "generator's frames carry no CRC, so crc only stops on a chance remainder")
+    ap.add_argument("--window-early-stop", default="", choices=["", "hda", "crc"],
+                    help="the same rules on the windowed schedule (td_set_window_stop; needs --window)")
     ap.add_argument("--min-iters", type=int, default=1, help="no frame stops before this many iterations")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
@@ -184,6 +186,10 @@ def main(argv=None):
             c.set_window(a.window, a.overlap, a.ext_scale, nii=a.nii, concurrent=a.concurrent)
         if a.early_stop:
             c.set_early_stop(a.early_stop, min_iters=a.min_iters)
+        if a.window_early_stop:
+            if not a.window:
+                ap.error("--window-early-stop needs --window (the exact schedule's rule is --early-stop)")
+            c.set_window_early_stop(a.window_early_stop, min_iters=a.min_iters)
         res = ber_sweep(c, pts, a.seed, a.max_frames, a.min_block_errors, a.batch,
                         log=lambda s: print(s, file=sys.stderr, flush=True))
     for p in res:

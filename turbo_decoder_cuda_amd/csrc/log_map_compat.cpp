@@ -31,7 +31,10 @@
 //                   CRC-24 is zero (crc); the flow_decoded rows after the stop are copies of the stop row
 //   TD_STOP_MIN_ITERS=n     no frame stops before n iterations (default 1)
 //   TD_STOP_CRC_POLY=0x...  the CRC generator's 24 low-order coefficients (default 0x800063, gCRC24B)
-// TD_EARLY_STOP together with TD_WINDOW is an error (the windowed schedule has no early termination).
+// TD_EARLY_STOP together with TD_WINDOW is an error: TD_EARLY_STOP is the exact schedule's switch.  The
+// windowed schedule has its own (td_set_window_stop), honoured only together with TD_WINDOW:
+//   TD_WINDOW_EARLY_STOP=hda|crc   the same rules on the windowed decode's rows; TD_STOP_MIN_ITERS and
+//                   TD_STOP_CRC_POLY apply.  Without TD_WINDOW it is an error.
 // A windowed schedule changes the arithmetic (sub-block boundaries): its results are gated by
 // the BER curve, not bit-exact.  Log_MAP_decoder always runs the exact SISO.
 #include <cstdio>
@@ -81,12 +84,18 @@ void set_schedule(td_handle* h)
         const char* poly = std::getenv("TD_STOP_CRC_POLY");
         sp.crc_poly = poly && *poly ? (uint32_t)std::strtoul(poly, nullptr, 0) : 0x800063u;
         if (W != 0) {
-            std::printf("turbo_mi355x: TD_EARLY_STOP and TD_WINDOW are both set: the windowed schedule has no early "
-                        "termination\n");
+            std::printf("turbo_mi355x: TD_EARLY_STOP and TD_WINDOW are both set: TD_EARLY_STOP is the exact schedule's "
+                        "rule (the windowed schedule's is TD_WINDOW_EARLY_STOP)\n");
             std::exit(1);
         }
         const int rc = td_set_early_stop(h, &sp);
         if (rc) die("td_set_early_stop (TD_EARLY_STOP / TD_STOP_MIN_ITERS / TD_STOP_CRC_POLY)", rc);
+    }
+    const char* ws = std::getenv("TD_WINDOW_EARLY_STOP");
+    if (ws && *ws && W == 0) {
+        std::printf("turbo_mi355x: TD_WINDOW_EARLY_STOP is set without TD_WINDOW: it is the windowed schedule's rule (the "
+                    "exact schedule's is TD_EARLY_STOP)\n");
+        std::exit(1);
     }
     if (W == 0) return;
     td_window_params w{};
@@ -100,6 +109,15 @@ void set_schedule(td_handle* h)
     if (rc) die("td_set_window_maxstar (TD_WINDOW_MAXSTAR)", rc);
     rc = td_set_window(h, &w);
     if (rc) die("td_set_window (TD_WINDOW / TD_OVERLAP / TD_EXT_SCALE)", rc);
+    if (ws && *ws) {
+        td_stop_params sp{};
+        sp.rule = std::strcmp(ws, "hda") == 0 ? TD_STOP_HDA : std::strcmp(ws, "crc") == 0 ? TD_STOP_CRC : -1;
+        sp.min_iters = env_int("TD_STOP_MIN_ITERS", 1);
+        const char* poly = std::getenv("TD_STOP_CRC_POLY");
+        sp.crc_poly = poly && *poly ? (uint32_t)std::strtoul(poly, nullptr, 0) : 0x800063u;
+        rc = td_set_window_stop(h, &sp);
+        if (rc) die("td_set_window_stop (TD_WINDOW_EARLY_STOP / TD_STOP_MIN_ITERS / TD_STOP_CRC_POLY)", rc);
+    }
 }
 
 void open_handle(int K)

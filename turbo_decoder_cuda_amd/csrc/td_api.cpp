@@ -109,6 +109,10 @@ struct td_handle {
     // early termination (td_set_early_stop): rule 0 = off
     td_stop_params stop{TD_STOP_NONE, 1, 0};
     uint32_t* d_crc = nullptr;      // [K] CRC syndromes by natural bit position (td_crc.h), built by td_set_early_stop
+                                    // or td_set_window_stop (a handle has a rule of one kind at most)
+    // early termination of the windowed schedule (td_set_window_stop): rule 0 = off
+    td_stop_params wstop{TD_STOP_NONE, 1, 0};
+    bool clk_stopped = false;       // the last decode ran the stopping windowed kernels (no clock sample)
     hipEvent_t ws_free = nullptr;   // recorded after the last decode's kernels
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
@@ -436,7 +440,7 @@ int groups_for(int B) { return (B + 7) / 8; }   // groups of 8 codewords, one wo
 // schedule), the alpha checkpoints of each decoder and the NII metrics [2 parity][2 dec][B][nS][2][8],
 // grown on demand
 struct WinCarve {
-    size_t arrK, arrC, nii, arrT, total;
+    size_t arrK, arrC, nii, arrT, arrS, total;
 };
 WinCarve win_carve(const td_handle* h, int B)
 {
@@ -448,7 +452,8 @@ WinCarve win_carve(const td_handle* h, int B)
     c.arrC = align_up(td::window_ckpt_elems(B, L, h->wp.window, elem == 4) * elem, 256);
     c.nii = align_up(c.nii, 256);
     c.arrT = align_up(td::window_bits_bytes(B, K), 256);
-    c.total = 2 * c.arrK + 2 * c.arrC + c.nii + c.arrT;
+    c.arrS = align_up(td::window_stop_bytes(B), 256);   // early termination: stop_at, evidence (always carved)
+    c.total = 2 * c.arrK + 2 * c.arrC + c.nii + c.arrT + c.arrS;
     return c;
 }
 
@@ -488,6 +493,8 @@ int window_bufs(td_handle* h, const td::DecodeParams<T>& dp, td::WindowBufs<T>& 
     wb.ckpt[1] = reinterpret_cast<T*>(w + 2 * arrK + arrC);   // the concurrent SISOs run together
     wb.nii = reinterpret_cast<T*>(w + 2 * arrK + 2 * arrC);
     wb.bitsT = reinterpret_cast<uint8_t*>(w + 2 * arrK + 2 * arrC + c.nii);
+    wb.stop_at = reinterpret_cast<int*>(w + 2 * arrK + 2 * arrC + c.nii + c.arrT);
+    wb.stop_ev = reinterpret_cast<unsigned*>(wb.stop_at) + ((size_t)dp.B + 63) / 64 * 64;
     return TD_OK;
 }
 
@@ -588,7 +595,11 @@ int decode_device_t(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int
                                 : td::launch_demux<T>(dp, static_cast<const T*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
-    if (h->wp.window) {
+    const bool wstop = h->wp.window && h->wstop.rule != TD_STOP_NONE;
+    if (wstop) {
+        const td::StopParams sp{h->wstop.rule, h->wstop.min_iters, h->d_crc, d_iters};
+        e = td::launch_window<T>(dp, h->wp, wb, st, h->wstr, &sp);
+    } else if (h->wp.window) {
         e = td::launch_window<T>(dp, h->wp, wb, st, h->wstr);   // streams made by td_set_window
     } else if (h->stop.rule != TD_STOP_NONE) {
         const td::StopParams sp{h->stop.rule, h->stop.min_iters, h->d_crc, d_iters};
@@ -596,11 +607,12 @@ int decode_device_t(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int
     } else {
         e = td::launch_turbo<T>(dp, st);
     }
-    // no rule (td_set_early_stop and td_set_window exclude each other): every codeword took them all
-    if (e == hipSuccess && d_iters && h->stop.rule == TD_STOP_NONE)
+    // no rule of either kind (td_set_early_stop, td_set_window_stop): every codeword took them all
+    if (e == hipSuccess && d_iters && h->stop.rule == TD_STOP_NONE && !wstop)
         e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
     if (e != hipSuccess) return hip_fail(e, h->wp.window ? "launch_window" : "launch_turbo");
     h->clk_valid = !capturing;
+    h->clk_stopped = wstop;
     if (ev) {
         TD_HIP(hipEventRecord(ev[2], st));
         ++h->nev;
@@ -940,7 +952,8 @@ int td_set_early_stop(td_handle* h, const td_stop_params* s)
     if (s->min_iters < 1 || s->min_iters > h->p.iterations)
         return fail(TD_EINVAL, "td_set_early_stop: min_iters must be in [1, iterations]");
     if (h->wp.window)
-        return fail(TD_EINVAL, "td_set_early_stop: the windowed schedule (td_set_window) has no early termination");
+        return fail(TD_EINVAL, "td_set_early_stop: the handle's schedule is windowed (td_set_window): its rule is set by "
+                               "td_set_window_stop");
     if (s->rule == TD_STOP_CRC) {
         if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
             return fail(TD_EINVAL, "td_set_early_stop: crc_poly must be the 24 low-order coefficients, non-zero");
@@ -957,6 +970,38 @@ int td_set_early_stop(td_handle* h, const td_stop_params* s)
         TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     h->stop = *s;
+    return TD_OK;
+}
+
+int td_set_window_stop(td_handle* h, const td_stop_params* s)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_window_stop: null handle");
+    if (!h->wp.window)
+        return fail(TD_EINVAL, "td_set_window_stop: the handle's schedule is not windowed (td_set_window first; the exact "
+                               "schedule's rule is td_set_early_stop)");
+    if (!s || s->rule == TD_STOP_NONE) {
+        h->wstop = td_stop_params{TD_STOP_NONE, 1, 0};
+        return TD_OK;
+    }
+    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_window_stop: unknown rule");
+    if (s->min_iters < 1 || s->min_iters > h->p.iterations)
+        return fail(TD_EINVAL, "td_set_window_stop: min_iters must be in [1, iterations]");
+    if (s->rule == TD_STOP_CRC) {
+        if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
+            return fail(TD_EINVAL, "td_set_window_stop: crc_poly must be the 24 low-order coefficients, non-zero");
+        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_window_stop: TD_STOP_CRC needs K > 24");
+        TD_HIP(hipSetDevice(h->p.device));
+        // the table lives on the device from here on: a decode allocates nothing for the rule
+        if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
+            h->d_crc = nullptr;
+            return fail(TD_ENOMEM, "td_set_window_stop: hipMalloc failed");
+        }
+        std::vector<uint32_t> tab((size_t)h->p.K);
+        td::crc24_syndromes(h->p.K, s->crc_poly, tab.data());
+        TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
+        TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    h->wstop = *s;
     return TD_OK;
 }
 
@@ -978,12 +1023,13 @@ int td_set_window(td_handle* h, const td_window_params* w)
     if (!h) return fail(TD_EINVAL, "td_set_window: null handle");
     if (!w || w->window == 0) {
         h->wp = td::WindowParams{0, 0, 0, 0, 1.0, 0, 0, 0, 0};
+        h->wstop = td_stop_params{TD_STOP_NONE, 1, 0};   // the windowed schedule's rule goes with it
         return TD_OK;
     }
     if (w->window < 3 || w->window > 10000) return fail(TD_EINVAL, "td_set_window: window must be 0 or in [3, 10000]");
     if (h->stop.rule != TD_STOP_NONE)
-        return fail(TD_EINVAL, "td_set_window: the handle has an early-termination rule (td_set_early_stop), which the "
-                               "windowed schedule does not support");
+        return fail(TD_EINVAL, "td_set_window: the handle has the exact schedule's early-termination rule "
+                               "(td_set_early_stop); turn it off first (the windowed schedule's is td_set_window_stop)");
     if (w->overlap < 0 || w->overlap > 3 * w->window)
         return fail(TD_EINVAL, "td_set_window: overlap must be in [0, 3*window]");
     if (!(w->ext_scale > 0.0) || !(w->ext_scale <= 4.0))
@@ -1055,6 +1101,9 @@ int td_clock_read(td_handle* h, double* sclk_ghz, double* span_ms)
 {
     if (!h) return fail(TD_EINVAL, "td_clock_read: null handle");
     if (!h->clk_valid) return fail(TD_EINVAL, "td_clock_read: the last decode was captured into a graph");
+    if (h->clk_stopped)
+        return fail(TD_EINVAL, "td_clock_read: the last decode ran the windowed schedule with early termination "
+                               "(td_set_window_stop), which takes no clock sample");
     TD_HIP(hipSetDevice(h->p.device));
     if (h->ws_pending && h->ws_free) TD_HIP(hipEventSynchronize(h->ws_free));   // this handle's last decode only
     unsigned long long v[4] = {};

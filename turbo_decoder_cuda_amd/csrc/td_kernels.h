@@ -126,11 +126,17 @@ struct WindowBufs {
     T* nii;        // [2 parity][2 dec][B][nS][2][8]
     T* ckpt[2];    // per decoder alpha checkpoints (window_ckpt_elems; serial: one shared)
     uint8_t* bitsT;  // [K][Bp] SISO2's decisions before bits_transpose_kernel (window_bits_bytes)
+    // early termination (td_set_window_stop), window_stop_bytes: per codeword of the padded batch, the
+    // iteration count it stopped after (0 = running) and this iteration's evidence word (HDA: 1 if a
+    // decision changed; CRC: the XOR of the syndromes of the 1-decisions, the row's CRC-24 remainder)
+    int* stop_at;        // [Bp]
+    unsigned* stop_ev;   // [Bp], right after stop_at (one reset covers both)
 };
 // sub-blocks per codeword (the last also takes L mod W) and the checkpoint scratch per decoder
 inline int window_subblocks(int L, int W) { return L / W > 0 ? L / W : 1; }
 size_t window_ckpt_elems(int B, int L, int W, bool f32);
 size_t window_bits_bytes(int B, int K);
+inline size_t window_stop_bytes(int B) { return (size_t)2 * ((B + 63) / 64 * 64) * sizeof(int); }
 // sub-blocks per lane run of the windowed kernels (1 = one sub-block per lane); `force` > 0 asks for
 // that many where runs are possible (g <= W, W a multiple of the checkpoint spacing S)
 int window_run(int L, int W, int g, int B, int ndec, int S, int force = 0);
@@ -143,7 +149,7 @@ struct WindowStreams {
 };
 template <typename T>
 hipError_t launch_window(const DecodeParams<T>& p, const WindowParams& w, const WindowBufs<T>& wb, hipStream_t st,
-                         const WindowStreams& ws);
+                         const WindowStreams& ws, const StopParams* stop = nullptr);   // stop: the stopping kernels
 
 template <typename T>
 hipError_t launch_siso(const DecodeParams<T>& p, const T* recs, const T* la, T* la_ws, int terminated, T* llr,

@@ -45,7 +45,8 @@ class TurboCodec:
         N.check(N.lib().td_create(C.byref(h), C.byref(p)))
         self._h = h
         self.device = int(device)
-        self.early_stop = None   # set_early_stop
+        self.early_stop = None   # set_early_stop / set_window_early_stop
+        self._window_stop = False   # the rule in self.early_stop is the windowed schedule's
 
     # -- lifetime (TurboCodingRelease) -------------------------------------------------
     def close(self) -> None:
@@ -106,6 +107,8 @@ class TurboCodec:
         w = N.TdWindowParams(int(window), int(overlap), int(bool(nii)), int(bool(concurrent)), float(ext_scale))
         N.check(N.lib().td_set_window(self._h, C.byref(w)))
         self.window = int(window)
+        if not self.window and self._window_stop:   # td_set_window(0) clears the windowed schedule's rule
+            self.early_stop, self._window_stop = None, False
 
     def set_early_stop(self, rule=None, min_iters: int = 1, crc_poly: int = N.CRC24B) -> None:
         """Per-codeword early termination of the exact schedule (td_set_early_stop): rule "hda" (a
@@ -118,6 +121,18 @@ class TurboCodec:
         N.check(N.lib().td_set_early_stop(self._h, C.byref(s)))
         self.early_stop = rule
 
+    def set_window_early_stop(self, rule=None, min_iters: int = 1, crc_poly: int = N.CRC24B) -> None:
+        """Per-codeword early termination of the windowed schedule (td_set_window_stop; after
+        set_window): the rules, arguments and frozen-row convention of set_early_stop, judged on the
+        windowed decode's own rows.  The rule survives later set_window calls with a window;
+        set_window(0) clears it."""
+        if rule not in _STOP_RULES:
+            raise ValueError(f"rule must be 'hda', 'crc' or None, got {rule!r}")
+        s = N.TdStopParams(_STOP_RULES[rule], int(min_iters), int(crc_poly) & 0xFFFFFFFF)
+        N.check(N.lib().td_set_window_stop(self._h, C.byref(s)))
+        self.early_stop = rule
+        self._window_stop = rule is not None
+
     def debug_window_layout(self, run: int = 0, run_a: int = 0, parts: int = 0) -> None:
         """Windowed kernels' layout for tests and measurements (td_debug_window_layout): sub-blocks
         per lane run (beta and alpha kernels) and batch parts; 0 = the layout's own choice."""
@@ -127,7 +142,8 @@ class TurboCodec:
     def TurboDecoding(self, flow: np.ndarray, return_le: bool = False, return_iters: bool = False):
         """flow [B, 3K+12] (or one row) -> out int32 [B, iterations, K] (the reference's
         flow_decoded rows); with return_le also Le [B, iterations, 2, K+3]; with return_iters also
-        the iterations each codeword used, int32 [B] (all `iterations` unless set_early_stop)."""
+        the iterations each codeword used, int32 [B] (all `iterations` unless set_early_stop or
+        set_window_early_stop)."""
         flow = np.ascontiguousarray(flow, dtype=self.dtype)
         one = flow.ndim == 1
         flow = flow.reshape(-1, stream_length(self.K))
@@ -228,7 +244,7 @@ class TurboCodec:
     def clock(self):
         """(sustained shader clock GHz, workgroup span ms) of the last decode: the exact schedule's
         turbo launch, or a windowed decode's last SISO2 beta workgroup (td_clock_read; waits for
-        this handle's last decode)."""
+        this handle's last decode).  A windowed decode with early termination takes no sample: an error."""
         g, s = C.c_double(), C.c_double()
         N.check(N.lib().td_clock_read(self._h, C.byref(g), C.byref(s)))
         return g.value, s.value
