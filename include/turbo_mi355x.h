@@ -308,6 +308,39 @@ int td_demodulate(const double* d_yi, const double* d_yq, long long nsym, int mo
 int td_count_errors(td_handle* h, const uint8_t* d_bits, int iters, const uint8_t* d_info, int B, int* d_err,
                     void* stream);
 
+/*
+ * LTE rate matching (3GPP TS 36.212 5.1.4.1) around the decoder's stream (an extension: ITTC/main.h:23-24
+ * declares rate_match / de_rate_match and the reference never defines them; the compat layer now does).
+ * The coded stream s[0..3K+12) of encoderm_turbo (log_map.cpp:566-578) is the three LTE streams
+ * interleaved, d_i(k) = s[3k+i], k < D = K+4 (the 12 tail values in order are d0_K, d1_K, d2_K, d0_K+1,
+ * ... of 5.1.3.2.2); no filler bits.  Sub-block interleaver: 32 columns, R = ceil(D/32) rows, Kpi = 32R,
+ * ND = Kpi - D leading <NULL>s.  Circular buffer: Kw = 3 Kpi entries, of which a soft buffer of Ncb <= Kw
+ * is used; a transmission of redundancy version rv reads the E non-NULL entries from
+ * k0 = R (2 ceil(Ncb / 8R) rv + 2) on, wrapping round w[0..Ncb) for as long as needed (E above the
+ * buffer's non-NULL count: repetition).
+ *   rate matching      e[b][k] = in[b][idx[k]], idx from the rule above
+ *   de-rate-matching   its transpose: d_llr[b][q] = the sum of every e[b][k] with idx[k] == q, added in
+ *                      ascending k in the buffer's own precision, starting from d_llr[b][q] itself with
+ *                      `accumulate` (HARQ combining of a retransmission into the soft buffer) and from
+ *                      +0.0 without; a position no k selects keeps its value (accumulate) or is 0.0.
+ *                      No atomics: the same bits on every run.  The output is td_decode_device's input.
+ * Ncb = 0 means Kw; otherwise Kpi <= Ncb <= Kw, else TD_EINVAL.  The first call builds and uploads the
+ * handle's tables; the launches then allocate nothing (they may be captured into a hipGraph).  It may be
+ * called again with another Ncb (it waits for the device first).
+ * TD_EINVAL: a null pointer, rv outside 0..3, E < 1, elem_size other than 1, 4 or 8 bytes, B < 0, a bad
+ * Ncb, a launch or an info call on a handle without tables.  B = 0 is a no-op.  Asynchronous on `stream`.
+ */
+int td_rm_set(td_handle* h, int Ncb);
+/* The layout the handle's tables were built for (any pointer may be null); n_nonnull = the non-NULL
+ * entries of w[0..Ncb). */
+int td_rm_info(td_handle* h, int* R, int* Kpi, int* Kw, int* Ncb, int* n_nonnull);
+/* d_in [B][3K+12] -> d_e [B][E], elements of elem_size bytes (1: uint8 bits, 4: float, 8: double). */
+int td_rate_match(td_handle* h, const void* d_in, int elem_size, int B, int rv, int E, void* d_e, void* stream);
+/* d_e [B][E] -> d_llr [B][3K+12]; both double for TD_F64, float for TD_F32. */
+int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d_llr, int accumulate, void* stream);
+/* Host only (no GPU, no handle): idx[k] = the stream position of e_k, k < E.  1 <= K <= 10000. */
+int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx);
+
 /* Last error message of this thread ("" if none). */
 const char* td_last_error(void);
 /* Number of visible HIP devices (0 on a host without a GPU; never fails). */

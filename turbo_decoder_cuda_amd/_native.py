@@ -29,6 +29,7 @@ EXPORTS = (
     "td_debug_placement_rule", "td_clock_read", "td_window_steps", "td_debug_placement_cost", "td_debug_window_layout",
     "td_debug_workspace_bytes", "td_set_window_maxstar", "td_set_early_stop", "td_decode_device_stop",
     "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
+    "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
 )
 
 
@@ -111,6 +112,12 @@ def lib() -> C.CDLL:
         L.td_crc24_syndromes.argtypes = [I, C.c_uint32, P]
     if hasattr(L, "td_set_window_stop"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_set_window_stop.argtypes = [P, C.POINTER(TdStopParams)]
+    if hasattr(L, "td_rm_set"):   # rate matching (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_rm_set.argtypes = [P, I]
+        L.td_rm_info.argtypes = [P] + [C.POINTER(C.c_int)] * 5
+        L.td_rate_match.argtypes = [P, P, I, I, I, I, P, P]
+        L.td_rate_dematch.argtypes = [P, P, I, I, I, P, I, P]
+        L.td_rm_index_host.argtypes = [I, I, I, I, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -8,6 +8,8 @@
 //   void TurboCodingRelease()                           log_map.cpp:1330-1345
 //   void AWGN(double*, double*, double, int)            log_map.cpp:1388-1400 (mgrns :1359-1374)
 //   void Log_MAP_decoder(double*, double*, int, double*, int)   log_map.cpp:898-1047
+//   void rate_match(int*, int, int*, int)               ITTC/main.h:23 (declared there, defined only here)
+//   void de_rate_match(double*, double*, int, int)      ITTC/main.h:24 (likewise; both run on the host)
 // and reads the caller's globals source_length / f1 / f2 (ITTC/main.h:6-11) without defining
 // them.  The decode runs on the MI355X through the C ABI (include/turbo_mi355x.h); nothing
 // here decodes on the CPU.  Reference behaviour kept on purpose:
@@ -215,6 +217,36 @@ void Log_MAP_decoder(double* recs, double* La, int terminated, double* LLR, int 
     if (!g_h) open_handle(L > 3 ? L - 3 : 1);
     const int rc = td_siso_host(g_h, recs, La, terminated, LLR, L, 1);
     if (rc) die("td_siso_host", rc);
+}
+
+// rate_match / de_rate_match (declared in ITTC/main.h:23-24, called from the commented-out lines
+// main.cpp:196,204, never defined by the reference): LTE rate matching of 36.212 5.1.4.1 at redundancy
+// version 0 over the whole circular buffer, on the host (td_rm_index_host).  K comes from the 3K+12
+// argument; the other length is E.
+static std::vector<int32_t> rm_index(const char* who, int stream_len, int E)
+{
+    if (stream_len < 15 || (stream_len - 12) % 3 || E < 1) {
+        std::printf("turbo_mi355x: %s: lengths %d (3K+12) and %d (E >= 1) do not fit\n", who, stream_len, E);
+        std::exit(1);
+    }
+    std::vector<int32_t> idx(E);
+    const int rc = td_rm_index_host((stream_len - 12) / 3, 0, 0, E, idx.data());
+    if (rc) die(who, rc);
+    return idx;
+}
+
+void rate_match(int* input, int in_len, int* output, int out_len)
+{
+    const std::vector<int32_t> idx = rm_index("rate_match", in_len, out_len);
+    for (int k = 0; k < out_len; ++k) output[k] = input[idx[k]];
+}
+
+// output[q] = the sum of the input[k] selected from stream position q, in ascending k; 0 where none was
+void de_rate_match(double* input, double* output, int in_len, int out_len)
+{
+    const std::vector<int32_t> idx = rm_index("de_rate_match", out_len, in_len);
+    for (int q = 0; q < out_len; ++q) output[q] = 0.0;
+    for (int k = 0; k < in_len; ++k) output[idx[k]] += input[k];
 }
 
 // mgrns (log_map.cpp:1359-1374): sum of 12 LCG uniforms per sample (CLT), support +-6 sigma.

@@ -17,6 +17,7 @@
 
 #include "td_crc.h"
 #include "td_kernels.h"
+#include "td_ratematch.h"
 
 #ifndef TD_SYS2_IN_TURBO
 #define TD_SYS2_IN_TURBO 1   // exact schedule: sys2 = sys1 o pi formed inside the turbo kernel (no demux_perm launch)
@@ -116,6 +117,12 @@ struct td_handle {
     hipEvent_t ws_free = nullptr;   // recorded after the last decode's kernels
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
+    // rate matching (td_rm_set): the host tables and their device copies, allocated once for the
+    // largest Ncb (3K+12 and Kw ints), so a later td_rm_set only uploads
+    td::RmTables rm;
+    int32_t* d_rm_rank = nullptr;
+    int32_t* d_rm_pos = nullptr;
+    bool rm_set = false;
 };
 
 namespace td {
@@ -908,6 +915,8 @@ int td_destroy(td_handle* h)
     if (h->d_crc) (void)hipFree(h->d_crc);
     if (h->d_win) (void)hipFree(h->d_win);
     if (h->d_wws) (void)hipFree(h->d_wws);
+    if (h->d_rm_rank) (void)hipFree(h->d_rm_rank);
+    if (h->d_rm_pos) (void)hipFree(h->d_rm_pos);
     release_wstr(h->wstr);
     for (auto& tri : h->ev)
         for (auto& e : tri) (void)hipEventDestroy(e);
@@ -1318,6 +1327,103 @@ int td_count_errors(td_handle* h, const uint8_t* d_bits, int iters, const uint8_
     if (!h || !d_bits || !d_info || !d_err || B < 1 || iters < 1) return fail(TD_EINVAL, "td_count_errors: bad argument");
     TD_HIP(hipSetDevice(h->p.device));
     TD_HIP(td::launch_count_errors(d_bits, d_info, h->p.K, iters, B, d_err, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_rm_set(td_handle* h, int Ncb)
+{
+    if (!h) return fail(TD_EINVAL, "td_rm_set: null handle");
+    td::RmTables t;
+    if (!td::rm_build(h->p.K, Ncb, t)) {
+        const int Kpi = 32 * ((h->p.K + 4 + 31) / 32);
+        return fail(TD_EINVAL, "td_rm_set: Ncb = " + std::to_string(Ncb) + " is neither 0 nor in [Kpi, Kw] = [" +
+                                   std::to_string(Kpi) + ", " + std::to_string(3 * Kpi) + "]");
+    }
+    TD_HIP(hipSetDevice(h->p.device));
+    if (!h->d_rm_rank && hipMalloc(&h->d_rm_rank, sizeof(int32_t) * t.rank.size()) != hipSuccess)
+        return fail(TD_ENOMEM, "td_rm_set: hipMalloc failed");
+    if (!h->d_rm_pos && hipMalloc(&h->d_rm_pos, sizeof(int32_t) * t.Kw) != hipSuccess)
+        return fail(TD_ENOMEM, "td_rm_set: hipMalloc failed");
+    TD_HIP(hipDeviceSynchronize());   // launches that still read the previous tables
+    h->rm_set = false;
+    TD_HIP(hipMemcpy(h->d_rm_rank, t.rank.data(), sizeof(int32_t) * t.rank.size(), hipMemcpyHostToDevice));
+    TD_HIP(hipMemcpy(h->d_rm_pos, t.pos.data(), sizeof(int32_t) * t.pos.size(), hipMemcpyHostToDevice));
+    h->rm = std::move(t);
+    h->rm_set = true;
+    return TD_OK;
+}
+
+int td_rm_info(td_handle* h, int* R, int* Kpi, int* Kw, int* Ncb, int* n_nonnull)
+{
+    if (!h) return fail(TD_EINVAL, "td_rm_info: null handle");
+    if (!h->rm_set) return fail(TD_EINVAL, "td_rm_info: call td_rm_set first");
+    if (R) *R = h->rm.R;
+    if (Kpi) *Kpi = h->rm.Kpi;
+    if (Kw) *Kw = h->rm.Kw;
+    if (Ncb) *Ncb = h->rm.Ncb;
+    if (n_nonnull) *n_nonnull = h->rm.Nnn;
+    return TD_OK;
+}
+
+namespace {
+
+// the argument checks td_rate_match and td_rate_dematch share; fills the launch's view of the tables
+int rm_launch_params(const char* who, td_handle* h, const void* a, const void* b, int B, int rv, int E, td::RmParams& p)
+{
+    const std::string w(who);
+    if (!h || !a || !b) return fail(TD_EINVAL, w + ": null argument");
+    if (!h->rm_set) return fail(TD_EINVAL, w + ": call td_rm_set first");
+    if (rv < 0 || rv > 3) return fail(TD_EINVAL, w + ": rv must be in 0..3");
+    if (E < 1) return fail(TD_EINVAL, w + ": E must be at least 1");
+    if (B < 0) return fail(TD_EINVAL, w + ": negative B");
+    p = td::RmParams{h->p.K, h->rm.R, h->rm.ND, h->rm.Nnn, h->rm.c0[rv], E, B, h->d_rm_rank, h->d_rm_pos};
+    return TD_OK;
+}
+
+}  // namespace
+
+int td_rate_match(td_handle* h, const void* d_in, int elem_size, int B, int rv, int E, void* d_e, void* stream)
+{
+    td::RmParams p;
+    if (const int rc = rm_launch_params("td_rate_match", h, d_in, d_e, B, rv, E, p)) return rc;
+    if (elem_size != 1 && elem_size != 4 && elem_size != 8)
+        return fail(TD_EINVAL, "td_rate_match: elem_size must be 1, 4 or 8 bytes");
+    if (B == 0) return TD_OK;
+    if (!td::launch_rate_match) return fail(TD_EHIP, "td_rate_match: this build has no td_ratematch.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    TD_HIP(td::launch_rate_match(p, d_in, elem_size, d_e, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d_llr, int accumulate, void* stream)
+{
+    td::RmParams p;
+    if (const int rc = rm_launch_params("td_rate_dematch", h, d_e, d_llr, B, rv, E, p)) return rc;
+    if (B == 0) return TD_OK;
+    if (!td::launch_rate_dematch<double> || !td::launch_rate_dematch<float>)
+        return fail(TD_EHIP, "td_rate_dematch: this build has no td_ratematch.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (h->p.precision == TD_F64)
+        TD_HIP(td::launch_rate_dematch<double>(p, static_cast<const double*>(d_e), static_cast<double*>(d_llr), accumulate, st));
+    else
+        TD_HIP(td::launch_rate_dematch<float>(p, static_cast<const float*>(d_e), static_cast<float*>(d_llr), accumulate, st));
+    return TD_OK;
+}
+
+int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx)
+{
+    if (!idx) return fail(TD_EINVAL, "td_rm_index_host: null idx");
+    if (rv < 0 || rv > 3) return fail(TD_EINVAL, "td_rm_index_host: rv must be in 0..3");
+    if (E < 1) return fail(TD_EINVAL, "td_rm_index_host: E must be at least 1");
+    td::RmTables t;
+    if (!td::rm_build(K, Ncb, t))
+        return fail(TD_EINVAL, "td_rm_index_host: K must be in [1, 10000] and Ncb 0 or in [Kpi, Kw]");
+    size_t j = (size_t)t.c0[rv];
+    for (int k = 0; k < E; ++k) {
+        idx[k] = t.pos[j];
+        if (++j == (size_t)t.Nnn) j = 0;
+    }
     return TD_OK;
 }
 

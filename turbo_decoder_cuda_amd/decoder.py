@@ -229,6 +229,71 @@ class TurboCodec:
                                               int(all_iters), C.c_void_p(le_ptr) if le_ptr else None,
                                               C.c_void_p(iters_ptr), C.c_void_p(stream_ptr) if stream_ptr else None))
 
+    # -- LTE rate matching (36.212 5.1.4.1; td_rm_set / td_rate_match / td_rate_dematch) ---
+    def set_rate_matching(self, Ncb: int = 0) -> dict:
+        """Build the handle's rate-matching tables for a soft buffer of Ncb entries (0: the whole
+        circular buffer Kw; otherwise Kpi <= Ncb <= Kw).  May be called again.  Returns the layout:
+        R, Kpi, Kw, Ncb and n_nonnull (the non-NULL entries of the buffer: E above it repeats)."""
+        N.check(N.lib().td_rm_set(self._h, int(Ncb)))
+        v = [C.c_int() for _ in range(5)]
+        N.check(N.lib().td_rm_info(self._h, *[C.byref(x) for x in v]))
+        self.rate_matching = dict(zip(("R", "Kpi", "Kw", "Ncb", "n_nonnull"), (x.value for x in v)))
+        return self.rate_matching
+
+    def _check_in(self, name, t, dtypes, cols=None) -> None:
+        """An input the rate-matching kernels read B * cols elements of."""
+        if t.dtype not in dtypes or not t.is_cuda or not t.is_contiguous() or t.ndim != 2:
+            raise ValueError(f"{name} must be a contiguous 2-D CUDA tensor of {' / '.join(map(str, dtypes))}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if cols is not None and t.shape[1] != cols:
+            raise ValueError(f"{name} must be [B, {cols}], got {tuple(t.shape)}")
+        if t.device.index != self.device:
+            raise ValueError(f"{name} is on {t.device}, the codec on cuda:{self.device}")
+
+    def rate_match(self, x, rv: int, E: int, out=None, stream=None):
+        """x: uint8 / float32 / float64 tensor [B, 3K+12] on this codec's device (coded bits, or any
+        per-position values) -> the E values a transmission of redundancy version rv carries,
+        [B, E] of x's dtype: x[:, rate_match_index(K, Ncb, rv, E)].  After set_rate_matching."""
+        import torch
+
+        self._check_in("x", x, (torch.uint8, torch.float32, torch.float64), stream_length(self.K))
+        rv, E, B = int(rv), int(E), x.shape[0]
+        if E < 1:
+            raise ValueError(f"E must be at least 1, got {E}")
+        if out is None:
+            out = torch.empty((B, E), dtype=x.dtype, device=x.device)
+        else:
+            self._check_out("out", out, x.dtype, (B, E), x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        N.check(N.lib().td_rate_match(self._h, C.c_void_p(x.data_ptr()), x.element_size(), B, rv, E,
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        return out
+
+    def rate_dematch(self, e, rv: int, out=None, accumulate: bool = False, stream=None):
+        """e: the received soft values [B, E] of a transmission of redundancy version rv, in the codec's
+        dtype -> LLRs [B, 3K+12] ready for decode: every position gets the sum of the e that were
+        selected from it (repetition), punctured positions 0.  With accumulate the sums are added
+        into `out` (required then): HARQ combining of a retransmission into the soft buffer."""
+        import torch
+
+        want = torch.float64 if self.precision == "f64" else torch.float32
+        self._check_in("e", e, (want,))
+        B, E = e.shape
+        if E < 1:
+            raise ValueError("e must have at least one column")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate adds into `out`: pass the soft buffer")
+            out = torch.empty((B, stream_length(self.K)), dtype=want, device=e.device)
+        else:
+            self._check_out("out", out, want, (B, stream_length(self.K)), e.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(e.device)
+        N.check(N.lib().td_rate_dematch(self._h, C.c_void_p(e.data_ptr()), B, int(rv), E, C.c_void_p(out.data_ptr()),
+                                        int(bool(accumulate)), C.c_void_p(stream.cuda_stream)))
+        return out
+
     # -- measurement ---------------------------------------------------------------------
     def profile(self, on: bool = True) -> None:
         """Bracket the next decodes' kernels with hipEvents (see td_profile_enable)."""
@@ -331,6 +396,15 @@ def demodulate(yi, yq, modulation: int, Kf: float, stream=None):
     N.check(N.lib().td_demodulate(C.c_void_p(yi.data_ptr()), C.c_void_p(yq.data_ptr()), yi.numel(), int(modulation),
                                   float(Kf), C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
     return out
+
+
+def rate_match_index(K: int, Ncb: int, rv: int, E: int) -> np.ndarray:
+    """int32 [E]: the stream position (index into the 3K+12 stream) of each value a transmission of
+    redundancy version rv carries, for a soft buffer of Ncb entries (0: the whole circular buffer).
+    Host only (td_rm_index_host): rate_match(x) is x[:, idx], rate_dematch its transpose."""
+    idx = np.empty(max(int(E), 0), dtype=np.int32)
+    N.check(N.lib().td_rm_index_host(int(K), int(Ncb), int(rv), int(E), idx.ctypes.data_as(C.c_void_p)))
+    return idx
 
 
 def TurboCodingInit(K: int, f1: int, f2: int, **kw) -> TurboCodec:
