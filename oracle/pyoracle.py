@@ -73,6 +73,9 @@ def lib():
             getattr(L, f"tdo_turbo_decode_window_{sfx}").argtypes = [C.POINTER(Trellis), P, P, C.c_int, C.c_int,
                                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                                     C.c_int, C.c_double, P, P]
+        for sfx in ("f64", "f32"):
+            getattr(L, f"tdo_spec_miss_siso_{sfx}").argtypes = [C.POINTER(Trellis), P, P, C.c_int, P, P]
+            getattr(L, f"tdo_spec_miss_turbo_{sfx}").argtypes = [C.POINTER(Trellis), P, P, C.c_int, C.c_int, P, P]
         L.tdo_decode_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int, P, C.c_int]
         L.tdo_synth_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, P, P]
         L.tdo_glibc_srand.argtypes = [C.POINTER(GlibcRand), C.c_uint]
@@ -173,6 +176,54 @@ def turbo_decode_window(flow: np.ndarray, K: int, f1: int, f2: int, iters: int, 
     fn = lib().tdo_turbo_decode_window_f32 if f32 else lib().tdo_turbo_decode_window_f64
     fn(C.byref(t), _p(pi), _p(flow), K, iters, algo, W, g, nrm, int(nii), int(concurrent), scale, _p(bits), _p(le))
     return bits.astype(np.uint8), le
+
+
+SPEC_WINDOW = 15   # the exact kernel's alpha window (TDO_SPEC_WINDOW)
+
+
+def spec_miss_siso(recs: np.ndarray, La: np.ndarray):
+    """The exact log-MAP kernel's speculation detector on one SISO pass (turbo_oracle_spec.inc):
+    (misses, per-window misses int32 [nT], harmful misses) in the precision of recs.  A miss is a
+    (step, state) pair of a speculated window (1 .. nT-2) whose unnormalised and exact max* buckets
+    differ; it is harmful when the two rows also give d another correction (most misses sit beside a
+    bucket edge, where they do not), so that only the recomputation keeps the decode exact."""
+    f32 = recs.dtype == np.float32
+    recs = np.ascontiguousarray(recs)
+    La = np.ascontiguousarray(La, dtype=recs.dtype)
+    L = La.size
+    win = np.zeros((L + SPEC_WINDOW - 1) // SPEC_WINDOW, dtype=np.int32)
+    t = trellis()
+    fn = lib().tdo_spec_miss_siso_f32 if f32 else lib().tdo_spec_miss_siso_f64
+    harm = C.c_int(0)
+    n = int(fn(C.byref(t), _p(recs), _p(La), L, _p(win), C.byref(harm)))
+    return n, win, harm.value
+
+
+def spec_miss_turbo(flow: np.ndarray, K: int, f1: int, f2: int, iters: int, harmful: bool = False):
+    """The detector over a log-MAP turbo decode of the batch flow [B, 3K+12] (or one row), summed over
+    iterations and both SISOs.  Returns (misses per codeword int64 [B], redo share): the share of
+    (group of 8 consecutive codewords, iteration, SISO, speculated window) executions with at least
+    one miss -- the kernel's alpha wave carries 8 codewords and recomputes the window for all of them.
+    With harmful also the harmful misses per codeword (spec_miss_siso), as a third value.
+    CPU counts on the oracle's arithmetic in flow's precision."""
+    f32 = flow.dtype == np.float32
+    flow = np.ascontiguousarray(flow).reshape(-1, 3 * K + 12)
+    B = flow.shape[0]
+    nT = (K + 3 + SPEC_WINDOW - 1) // SPEC_WINDOW
+    t = trellis()
+    pi = qpp(K, f1, f2)
+    fn = lib().tdo_spec_miss_turbo_f32 if f32 else lib().tdo_spec_miss_turbo_f64
+    win = np.zeros((B, iters, 2, nT), dtype=np.int32)
+    total, harm = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        h = C.c_int(0)
+        total[b] = fn(C.byref(t), _p(pi), _p(flow[b]), K, iters, _p(win[b]), C.byref(h))
+        harm[b] = h.value
+    assert np.array_equal(win.sum(axis=(1, 2, 3)), total)
+    spec = win[..., 1:nT - 1]                     # the speculated windows
+    hit = np.array([(spec[g:g + 8] > 0).any(axis=0) for g in range(0, B, 8)])
+    share = float(hit.mean()) if hit.size else 0.0
+    return (total, share, harm) if harmful else (total, share)
 
 
 def decode_batch(flow: np.ndarray, K: int, f1: int, f2: int, iters: int, algo: int = ALGO_LOGMAP,

@@ -424,6 +424,7 @@ void tdo_demultiplex(const double* flow, int K, const int* pi, double* yk) { dem
 #define MAXSTAR_Q(x, y) tdo_maxstar_q((x), (y))
 #include "turbo_oracle_siso.inc"
 #include "turbo_oracle_window.inc"
+#include "turbo_oracle_spec.inc"
 #undef REAL
 #undef SFX
 #undef MAXSTAR
@@ -435,6 +436,7 @@ void tdo_demultiplex(const double* flow, int K, const int* pi, double* yk) { dem
 #define MAXSTAR_Q(x, y) tdo_maxstar_q_f32((x), (y))
 #include "turbo_oracle_siso.inc"
 #include "turbo_oracle_window.inc"
+#include "turbo_oracle_spec.inc"
 #undef REAL
 #undef SFX
 #undef MAXSTAR

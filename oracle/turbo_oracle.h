@@ -131,6 +131,26 @@ void tdo_window_siso_f32(const tdo_trellis* t, const float* ys, const float* yp,
                          float* new_a, float* new_b, float* LLR);
 
 /*
+ * The exact log-MAP kernel's speculation detector, restated (turbo_oracle_spec.inc; td_kernels.hip
+ * AlphaSchedS / kASpec): the number of (step, state) pairs of the alpha pass whose max* bucket
+ * (td_tables.h BucketBits) of the unnormalised difference differs from the bucket of the exact one,
+ * over the windows the kernel speculates on (1 .. nT-2 of TDO_SPEC_WINDOW steps, nT = ceil(L/15)).
+ * _siso: one SISO pass, win_miss (nullable) [nT] per-window counts.  _turbo: tdo_turbo_decode's
+ * log-MAP loop, win_miss (nullable) [iters][2][nT]; returns the sum over iterations and both SISOs.
+ * *harm (nullable): how many of the misses read another correction from the speculated row than from
+ * the exact one (the others sit beside a bucket edge, where both rows give the same value).
+ */
+#define TDO_SPEC_WINDOW 15
+int tdo_spec_miss_siso_f64(const tdo_trellis* t, const double* recs, const double* La, int L, int* win_miss,
+                           int* harm);
+int tdo_spec_miss_siso_f32(const tdo_trellis* t, const float* recs, const float* La, int L, int* win_miss,
+                           int* harm);
+int tdo_spec_miss_turbo_f64(const tdo_trellis* t, const int* pi, const double* flow, int K, int iters,
+                            int* win_miss, int* harm);
+int tdo_spec_miss_turbo_f32(const tdo_trellis* t, const int* pi, const float* flow, int K, int iters,
+                            int* win_miss, int* harm);
+
+/*
  * Batch front-end used for the CPU baseline and the parity tests: B codewords, each flow row
  * of 3K+12 values (f64 or f32 by `f32`), nthreads host threads (codewords dealt round-robin).
  * bits[B][K] = final-iteration hard bits (uint8).  Returns 0.

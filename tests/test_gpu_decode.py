@@ -457,7 +457,8 @@ np.savez(sys.argv[3], **out)
 def test_alpha_speculation_redo_path_is_exact(tmp_path):
     """The log-MAP alpha window reads its max* rows speculatively and recomputes a window in the
     committed order when a bucket check fails (td_kernels.hip kASpec), which practically never
-    happens on real data.  libturbo_mi355x_redo.so (build.py, -DTD_ASPEC_REDO) takes the redo on
+    happens on continuous LLRs (on fixed-point ones it does: test_gpu_quantised_inputs.py).
+    libturbo_mi355x_redo.so (build.py, -DTD_ASPEC_REDO) takes the redo on
     every window: its bits and Le equal the production library's bit for bit, fp64 and fp32, on
     the reference's K = 1024 frames and a K = 6144 batch (and the fp64 bits the reference's)."""
     redo = os.path.join(PKG, "libturbo_mi355x_redo.so")

@@ -1116,8 +1116,12 @@ __device__ __forceinline__ void astore_row(T* sa, unsigned voff, T v)
 // bit-identical to the committed order.  A window with any mismatch in any lane is recomputed in
 // the committed order from its first alpha (alpha_window), stores included, before the barrier:
 // the two differences differ by roundings of the normalisation only, so a mismatch needs d within
-// a few ulps of a bucket edge and the redo practically never runs (TD_ASPEC_REDO forces it on
-// every window: that build must and does decode bit-identically).  One box, 3 interleaved rounds
+// a few ulps of a bucket edge.  On continuous LLRs (the benchmark's AWGN frames) that practically
+// never happens; on fixed-point LLRs (multiples of a quantum, saturated) d sits exactly on an edge
+// in thousands of steps and 8-28 % of a wave's windows are recomputed (CPU counts of
+// oracle/turbo_oracle_spec.inc; what that costs on the GPU is not measured).
+// TD_ASPEC_REDO forces the redo on every window: that build must and does decode bit-identically.
+// One box, 3 interleaved rounds
 // (profiles/r04/ab_v31_aspec.txt): config 2 1502 -> 1521 Mbit/s (+1.3 %), fp32 log-MAP +0.4 %, the
 // 32768 shard level; the fp32 four-per-CU kernel of the 12-step TU lost 3.4 %, so it keeps the
 // committed order.  (With the flag left to the compiler, and with SLP packing the two buckets into
