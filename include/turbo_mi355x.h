@@ -38,13 +38,14 @@ enum td_algo {
 /* Arithmetic of the decode. */
 enum td_precision {
     TD_F64 = 0,   /* IEEE fp64 with the reference's operation order: the parity mode */
-    TD_F32 = 1    /* fp32, same schedule and op order (throughput mode) */
+    TD_F32 = 1,   /* fp32, same schedule and op order (throughput mode) */
+    TD_FIXED = 2  /* fixed point: int8 channel LLRs, integer Max-Log-MAP, int16 extrinsics (below) */
 };
 
 /* Code and schedule parameters.  Reference: globals source_length/f1/f2 (ITTC/main.h:6-11,
  * main.cpp:29-37), macros N_ITERATION / TERMINATED / TYPE_DECODER (ITTC/log_map.h:24-30). */
 typedef struct td_params {
-    int K;            /* information bits per codeword, 1 <= K <= 10000 (MAX_FRAME_LENGTH) */
+    int K;            /* information bits per codeword, 1 <= K <= 10000 (MAX_FRAME_LENGTH); TD_FIXED: K >= 8 */
     int f1, f2;       /* QPP interleaver: pi(i) = (f1*i + f2*i*i) mod K (log_map.cpp:616-624) */
     int iterations;   /* turbo iterations (N_ITERATION) */
     int algo;         /* enum td_algo */
@@ -218,6 +219,45 @@ int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le
 uint32_t td_crc24_host(const uint8_t* bits, int K, uint32_t poly);
 int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table /* [K] */);
 
+/*
+ * The fixed-point decoder, precision TD_FIXED (an extension: ITTC/main.h:21-24 declares TurboDecodingfixpoint
+ * and the reference never defines it).  The decoder an LTE receiver with an int8 soft buffer uses: exact
+ * full-trellis schedule, TD_ALGO_MAXLOG only, K >= 8 (td_create: TD_EINVAL otherwise).  All values are
+ * integers:
+ *   input      q[3K+12] int8 in the reference stream layout; -128 is read as -127.
+ *   demultiplex  as log_map.cpp:1083-1127 without the x0.5: xs1, xp1, xs2 = xs1 o pi, xp2, each K+3 long.
+ *   SISO       branch metric of state s, input u at position i: (2u-1)(xs[i] + La[i]) + o_u(s) xp[i], with
+ *              o_u(s) = +-1 the branch's parity (twice the float decoder's metric).  alpha and beta with
+ *              plain max, both terminated in state 0.  Lambda[i] = max over the u = 1 branches of
+ *              alpha + gamma + beta, minus the same over u = 0; LLR[i] = Lambda[i] >> 1 (Lambda is even).
+ *   iteration  as log_map.cpp:1217-1265: La = deinterleaved Le (tails 0), SISO1, Le = f(LLR - La - xs1),
+ *              interleave, SISO2, Le = f(LLR - La - xs2), hard bit = (LLR < 0) ? 0 : 1, deinterleaved.
+ *   f(r)       clamp(sign(r) ((|r| ext_scale_q) >> 2), -le_max, +le_max): the extrinsic scaled by
+ *              ext_scale_q quarters, truncated towards zero, clamped.
+ * Nothing else saturates: the state metrics are wide enough for any int8 input and any allowed
+ * parameters.  With ext_scale_q = 4 and no clamp in effect the decode equals the fp64
+ * Max-Log-MAP decode of the same integers, bits and Le.
+ * On a TD_FIXED handle td_decode_device / td_decode_device_stop / td_decode_host / td_decode_host_stop take
+ * int8 LLRs [B][3K+12] (not modified) and give the bits as ever and d_le / le as int16
+ * [B][iterations][2][K+3]; the _stop forms fill the counts with `iterations` (early termination of the
+ * fixed decoder does not exist yet).  Asynchronous, one workspace, event ordering and capture as
+ * documented at td_decode_device.  td_reserve sizes the workspace with a plain allocation (no placement
+ * search); after it a decode allocates nothing and may be captured into a hipGraph.  td_profile_read
+ * reports the demultiplex (the transpose of the int8 stream into the workspace) and the decode.
+ * td_rate_dematch takes int8 d_e and int8 d_llr (see there); td_rate_match with elem_size 1 moves int8.
+ * TD_EINVAL on a TD_FIXED handle, never silently ignored: td_set_window, td_set_window_maxstar,
+ * td_set_early_stop, td_set_window_stop, td_siso_host, td_clock_read, td_debug_set_stamps.
+ *
+ * td_set_fixed: le_max in [1, 255], ext_scale_q in [1, 4] (quarters; 4 = no scaling); the default is
+ * {255, 3}, which NULL restores.  TD_EINVAL on a handle of another precision or a value out of range; a
+ * failed call leaves the setting as it was.
+ */
+typedef struct td_fixed_params {
+    int le_max;        /* the extrinsic's clamp */
+    int ext_scale_q;   /* the extrinsic's scale in quarters */
+} td_fixed_params;
+int td_set_fixed(td_handle* h, const td_fixed_params* f);
+
 /* Kernel timing (measurement support): while enabled, hipEvents on the decode stream bracket
  * the demultiplex kernel and the turbo kernel of every td_decode_device call.
  * td_profile_read synchronises on them, returns the average durations (ms) over the
@@ -336,7 +376,10 @@ int td_rm_set(td_handle* h, int Ncb);
 int td_rm_info(td_handle* h, int* R, int* Kpi, int* Kw, int* Ncb, int* n_nonnull);
 /* d_in [B][3K+12] -> d_e [B][E], elements of elem_size bytes (1: uint8 bits, 4: float, 8: double). */
 int td_rate_match(td_handle* h, const void* d_in, int elem_size, int B, int rv, int E, void* d_e, void* stream);
-/* d_e [B][E] -> d_llr [B][3K+12]; both double for TD_F64, float for TD_F32. */
+/* d_e [B][E] -> d_llr [B][3K+12]; both double for TD_F64, float for TD_F32, int8 for TD_FIXED.  In int8
+ * each position is the sum of its e in ascending k saturated to [-127, 127] after every addition, starting
+ * from d_llr itself (-128 read as -127) with `accumulate` and from 0 without; a position no k selects
+ * keeps its value (accumulate) or is 0. */
 int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d_llr, int accumulate, void* stream);
 /* Host only (no GPU, no handle): idx[k] = the stream position of e_k, k < E.  1 <= K <= 10000. */
 int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx);

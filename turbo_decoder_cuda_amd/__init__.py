@@ -5,7 +5,7 @@ csrc/).  This package holds its build script and a thin host-side mirror of the 
 codec interface (decoder.py).  See DESIGN.md.
 """
 from .decoder import (N_ITERATION, TERMINATED, TurboCodec, TurboCodingInit, demodulate, device_count, modulate,
-                      rate_match_index, stream_length)
+                      quantise, rate_match_index, stream_length)
 
 __all__ = ["TurboCodec", "TurboCodingInit", "N_ITERATION", "TERMINATED", "device_count", "stream_length",
-           "modulate", "demodulate", "rate_match_index"]
+           "modulate", "demodulate", "rate_match_index", "quantise"]

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("TD_LIB_PATH") or os.path.join(PKG, "libturbo_mi355x.s
 
 TD_OK, TD_EINVAL, TD_ENOMEM, TD_EHIP, TD_ENODEV = 0, 1, 2, 3, 4
 TD_ALGO_LOGMAP, TD_ALGO_MAXLOG = 0, 1
-TD_F64, TD_F32 = 0, 1
+TD_F64, TD_F32, TD_FIXED = 0, 1, 2
 TD_WMAXSTAR_FAST, TD_WMAXSTAR_EXACT = 0, 1
 TD_MAXSTAR_WINDOW_FAST = 2   # td_maxstar_host_* algo: the windowed one-read table
 TD_STOP_NONE, TD_STOP_HDA, TD_STOP_CRC = 0, 1, 2
@@ -30,6 +30,7 @@ EXPORTS = (
     "td_debug_workspace_bytes", "td_set_window_maxstar", "td_set_early_stop", "td_decode_device_stop",
     "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
     "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
+    "td_set_fixed",
 )
 
 
@@ -47,6 +48,10 @@ class TdWindowParams(C.Structure):
 
 class TdStopParams(C.Structure):
     _fields_ = [("rule", C.c_int), ("min_iters", C.c_int), ("crc_poly", C.c_uint32)]
+
+
+class TdFixedParams(C.Structure):
+    _fields_ = [("le_max", C.c_int), ("ext_scale_q", C.c_int)]
 
 
 class TurboError(RuntimeError):
@@ -118,6 +123,8 @@ def lib() -> C.CDLL:
         L.td_rate_match.argtypes = [P, P, I, I, I, I, P, P]
         L.td_rate_dematch.argtypes = [P, P, I, I, I, P, I, P]
         L.td_rm_index_host.argtypes = [I, I, I, I, P]
+    if hasattr(L, "td_set_fixed"):   # the fixed-point decoder (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_set_fixed.argtypes = [P, C.POINTER(TdFixedParams)]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

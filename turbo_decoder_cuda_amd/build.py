@@ -72,7 +72,8 @@ def _workers(n: int) -> int:
 # td_kernels_win.hip (the sub-block schedule) under the max-ILP machine scheduler: +1.4 % at BASELINE
 # config 5; the exact kernels (td_kernels.hip) lose 1 % under it and keep the default.
 WIN_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-SRCS = ("td_kernels.hip", "td_kernels_w12.hip", "td_kernels_win.hip", "td_synth.hip", "td_ratematch.hip", "td_api.cpp")
+SRCS = ("td_kernels.hip", "td_kernels_w12.hip", "td_kernels_win.hip", "td_synth.hip", "td_ratematch.hip", "td_fixed.hip",
+        "td_api.cpp")
 FILE_FLAGS = {"td_kernels_win.hip": WIN_FLAGS}
 
 

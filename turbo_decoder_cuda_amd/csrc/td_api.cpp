@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "td_crc.h"
+#include "td_fixed.h"
 #include "td_kernels.h"
 #include "td_ratematch.h"
 
@@ -123,6 +124,8 @@ struct td_handle {
     int32_t* d_rm_rank = nullptr;
     int32_t* d_rm_pos = nullptr;
     bool rm_set = false;
+    // the fixed-point decoder (TD_FIXED): the extrinsic's clamp and scale (td_set_fixed)
+    td_fixed_params fxp{255, 3};
 };
 
 namespace td {
@@ -632,6 +635,99 @@ int decode_device_t(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int
     return TD_OK;
 }
 
+bool is_fixed(const td_handle* h) { return h->p.precision == TD_FIXED; }
+
+int not_fixed(const td_handle* h, const char* who)
+{
+    if (!is_fixed(h)) return TD_OK;
+    return fail(TD_EINVAL, std::string(who) + ": not available on a fixed-point handle (TD_FIXED)");
+}
+
+// the fixed-point decoder's workspace for B codewords: a plain allocation, grown and never shrunk
+int ensure_fixed_ws(td_handle* h, int B)
+{
+    const td::FxCarve c = td::fx_carve(B, h->p.K, h->p.iterations);
+    if (c.total <= h->ws_bytes) return TD_OK;
+    if (h->d_ws) {
+        TD_HIP(hipDeviceSynchronize());
+        TD_HIP(ws_release(h->d_ws));
+        h->d_ws = nullptr;
+        h->ws_bytes = 0;
+    }
+    if (ws_malloc(&h->d_ws, c.total) != hipSuccess) {
+        h->d_ws = nullptr;
+        return fail(TD_ENOMEM, "hipMalloc of the decode workspace failed (" + std::to_string(c.total) + " B)");
+    }
+    h->ws_bytes = c.total;
+    return TD_OK;
+}
+
+// td_decode_device on a TD_FIXED handle: the workspace event and profiling protocol of decode_device_t
+int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le, int32_t* d_iters,
+                 hipStream_t st)
+{
+    if (!td::launch_fixed_demux || !td::launch_fixed_turbo)
+        return fail(TD_EHIP, "td_decode_device: this build has no td_fixed.hip");
+    int rc = ensure_fixed_ws(h, B);
+    if (rc) return rc;
+    const td::FxCarve c = td::fx_carve(B, h->p.K, h->p.iterations);
+    char* ws = static_cast<char*>(h->d_ws);
+    td::fx::FxArgs a{};
+    a.xs = reinterpret_cast<int8_t*>(ws + c.xs);
+    a.xp1 = reinterpret_cast<int8_t*>(ws + c.xp1);
+    a.xp2 = reinterpret_cast<int8_t*>(ws + c.xp2);
+    a.ext12 = reinterpret_cast<int16_t*>(ws + c.ext12);
+    a.ext21 = reinterpret_cast<int16_t*>(ws + c.ext21);
+    a.ckpt = reinterpret_cast<int32_t*>(ws + c.ckpt);
+    a.bitsT = reinterpret_cast<uint8_t*>(ws + c.bitsT);
+    a.le = static_cast<int16_t*>(d_le);
+    a.pi = h->d_pi;
+    a.pinv = h->d_pinv;
+    a.K = h->p.K;
+    a.L = h->p.K + td::kMemory;
+    a.B = B;
+    a.iters = h->p.iterations;
+    a.all_iters = all_iters ? 1 : 0;
+    a.le_max = h->fxp.le_max;
+    a.scale_q = h->fxp.ext_scale_q;
+    a.Bp = c.Bp;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    TD_HIP(hipStreamIsCapturing(st, &cap));
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    if (!capturing) {
+        if (!h->ws_free) TD_HIP(hipEventCreateWithFlags(&h->ws_free, hipEventDisableTiming));
+        if (h->ws_pending && st != h->ws_stream) TD_HIP(hipStreamWaitEvent(st, h->ws_free, 0));
+    }
+    hipEvent_t* ev = nullptr;
+    if (h->prof && !capturing) {
+        if (h->nev == h->ev.size()) {
+            std::array<hipEvent_t, 3> tri{};
+            for (auto& x : tri) TD_HIP(hipEventCreate(&x));
+            h->ev.push_back(tri);
+        }
+        ev = h->ev[h->nev].data();
+        TD_HIP(hipEventRecord(ev[0], st));
+    }
+    hipError_t e = td::launch_fixed_demux(a, static_cast<const int8_t*>(d_llr), st);
+    if (e != hipSuccess) return hip_fail(e, "launch_fixed_demux");
+    if (ev) TD_HIP(hipEventRecord(ev[1], st));
+    e = td::launch_fixed_turbo(a, d_bits, st);
+    if (e == hipSuccess && d_iters)   // no early termination in fixed point: every codeword takes them all
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
+    if (e != hipSuccess) return hip_fail(e, "launch_fixed_turbo");
+    h->clk_valid = false;
+    if (ev) {
+        TD_HIP(hipEventRecord(ev[2], st));
+        ++h->nev;
+    }
+    if (!capturing) {
+        TD_HIP(hipEventRecord(h->ws_free, st));
+        h->ws_stream = st;
+        h->ws_pending = true;
+    }
+    return TD_OK;
+}
+
 template <typename T>
 int siso_host_t(td_handle* h, const void* recs, const void* La, int terminated, void* LLR, int L, int B)
 {
@@ -804,7 +900,11 @@ int td_create(td_handle** out, const td_params* p)
     if (p->K < 1 || p->K > 10000) return fail(TD_EINVAL, "td_create: K must be in [1, 10000] (MAX_FRAME_LENGTH)");
     if (p->iterations < 1 || p->iterations > 64) return fail(TD_EINVAL, "td_create: iterations must be in [1, 64]");
     if (p->algo != TD_ALGO_LOGMAP && p->algo != TD_ALGO_MAXLOG) return fail(TD_EINVAL, "td_create: bad algo");
-    if (p->precision != TD_F64 && p->precision != TD_F32) return fail(TD_EINVAL, "td_create: bad precision");
+    if (p->precision != TD_F64 && p->precision != TD_F32 && p->precision != TD_FIXED)
+        return fail(TD_EINVAL, "td_create: bad precision");
+    if (p->precision == TD_FIXED && p->algo != TD_ALGO_MAXLOG)
+        return fail(TD_EINVAL, "td_create: TD_FIXED decodes with TD_ALGO_MAXLOG only");
+    if (p->precision == TD_FIXED && p->K < 8) return fail(TD_EINVAL, "td_create: TD_FIXED needs K >= 8");
     // the QPP table must be a permutation (gen_qpp_index does not check; a bad f1/f2 silently
     // breaks the reference -- here it is an error)
     std::vector<int> pi(p->K);
@@ -827,7 +927,7 @@ int td_create(td_handle** out, const td_params* p)
 
     td_handle* h = new td_handle();
     h->p = *p;
-    h->elem = p->precision == TD_F64 ? sizeof(double) : sizeof(float);
+    h->elem = p->precision == TD_F64 ? sizeof(double) : p->precision == TD_F32 ? sizeof(float) : sizeof(int8_t);
     {
         h->role_cus = prop.multiProcessorCount;
         const char* o3 = std::getenv("TD_OCC3");      // 0: large batches stay on two workgroups per CU
@@ -929,6 +1029,7 @@ int td_reserve(td_handle* h, int B)
 {
     if (!h || B < 1) return fail(TD_EINVAL, "td_reserve: bad argument");
     TD_HIP(hipSetDevice(h->p.device));
+    if (is_fixed(h)) return ensure_fixed_ws(h, B);   // a plain allocation: no placement search
     const int rc = place_ws(h, groups_for(B));
     if (rc || !h->wp.window) return rc;
     return ensure_wws(h, win_carve(h, B).total);   // the windowed schedule's buffers as well
@@ -940,6 +1041,7 @@ int td_decode_device_stop(td_handle* h, const void* d_llr, int B, uint8_t* d_bit
     if (!h || !d_llr || !d_bits || B < 1) return fail(TD_EINVAL, "td_decode_device: bad argument");
     TD_HIP(hipSetDevice(h->p.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (is_fixed(h)) return decode_fixed(h, d_llr, B, d_bits, all_iters, d_le, d_iters, st);
     if (h->p.precision == TD_F64) return decode_device_t<double>(h, d_llr, B, d_bits, all_iters, d_le, d_iters, st);
     return decode_device_t<float>(h, d_llr, B, d_bits, all_iters, d_le, d_iters, st);
 }
@@ -953,6 +1055,7 @@ int td_decode_device(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, in
 int td_set_early_stop(td_handle* h, const td_stop_params* s)
 {
     if (!h) return fail(TD_EINVAL, "td_set_early_stop: null handle");
+    if (const int nf = not_fixed(h, "td_set_early_stop")) return nf;
     if (!s || s->rule == TD_STOP_NONE) {
         h->stop = td_stop_params{TD_STOP_NONE, 1, 0};
         return TD_OK;
@@ -985,6 +1088,7 @@ int td_set_early_stop(td_handle* h, const td_stop_params* s)
 int td_set_window_stop(td_handle* h, const td_stop_params* s)
 {
     if (!h) return fail(TD_EINVAL, "td_set_window_stop: null handle");
+    if (const int nf = not_fixed(h, "td_set_window_stop")) return nf;
     if (!h->wp.window)
         return fail(TD_EINVAL, "td_set_window_stop: the handle's schedule is not windowed (td_set_window first; the exact "
                                "schedule's rule is td_set_early_stop)");
@@ -1027,9 +1131,25 @@ int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table)
     return TD_OK;
 }
 
+int td_set_fixed(td_handle* h, const td_fixed_params* f)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed: the handle is not fixed-point (TD_FIXED)");
+    if (!f) {
+        h->fxp = td_fixed_params{255, 3};
+        return TD_OK;
+    }
+    if (f->le_max < 1 || f->le_max > 255) return fail(TD_EINVAL, "td_set_fixed: le_max must be in [1, 255]");
+    if (f->ext_scale_q < 1 || f->ext_scale_q > 4)
+        return fail(TD_EINVAL, "td_set_fixed: ext_scale_q must be in [1, 4] (quarters; 4 = no scaling)");
+    h->fxp = *f;
+    return TD_OK;
+}
+
 int td_set_window(td_handle* h, const td_window_params* w)
 {
     if (!h) return fail(TD_EINVAL, "td_set_window: null handle");
+    if (const int nf = not_fixed(h, "td_set_window")) return nf;
     if (!w || w->window == 0) {
         h->wp = td::WindowParams{0, 0, 0, 0, 1.0, 0, 0, 0, 0};
         h->wstop = td_stop_params{TD_STOP_NONE, 1, 0};   // the windowed schedule's rule goes with it
@@ -1054,6 +1174,7 @@ int td_set_window(td_handle* h, const td_window_params* w)
 int td_set_window_maxstar(td_handle* h, int form)
 {
     if (!h) return fail(TD_EINVAL, "td_set_window_maxstar: null handle");
+    if (const int nf = not_fixed(h, "td_set_window_maxstar")) return nf;
     if (form != TD_WMAXSTAR_FAST && form != TD_WMAXSTAR_EXACT)
         return fail(TD_EINVAL, "td_set_window_maxstar: form must be TD_WMAXSTAR_FAST or TD_WMAXSTAR_EXACT");
     h->win_exact_table = form == TD_WMAXSTAR_EXACT ? 1 : 0;
@@ -1109,6 +1230,7 @@ int td_profile_read(td_handle* h, float* demux_ms, float* decode_ms, int* launch
 int td_clock_read(td_handle* h, double* sclk_ghz, double* span_ms)
 {
     if (!h) return fail(TD_EINVAL, "td_clock_read: null handle");
+    if (const int nf = not_fixed(h, "td_clock_read")) return nf;
     if (!h->clk_valid) return fail(TD_EINVAL, "td_clock_read: the last decode was captured into a graph");
     if (h->clk_stopped)
         return fail(TD_EINVAL, "td_clock_read: the last decode ran the windowed schedule with early termination "
@@ -1127,6 +1249,7 @@ int td_clock_read(td_handle* h, double* sclk_ghz, double* span_ms)
 int td_debug_set_stamps(td_handle* h, void* d_buf)
 {
     if (!h) return fail(TD_EINVAL, "td_debug_set_stamps: null handle");
+    if (const int nf = not_fixed(h, "td_debug_set_stamps")) return nf;
     h->stamps = d_buf;
     return TD_OK;
 }
@@ -1185,7 +1308,7 @@ int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le
     const size_t n = 3 * (size_t)K + 4 * td::kMemory;
     const size_t in_b = (size_t)B * n * h->elem;
     const size_t bits_b = (size_t)B * it * K;
-    const size_t le_b = le ? (size_t)B * it * 2 * L * h->elem : 0;
+    const size_t le_b = le ? (size_t)B * it * 2 * L * (is_fixed(h) ? sizeof(int16_t) : h->elem) : 0;
     // staging buffers kept by the handle (grown on demand), so a warm per-frame caller allocates nothing
     auto grow = [](void** p, size_t& cap, size_t need) {
         if (need <= cap) return hipSuccess;
@@ -1215,6 +1338,7 @@ int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le
 int td_siso_host(td_handle* h, const void* recs, const void* La, int terminated, void* LLR, int L, int B)
 {
     if (!h || !recs || !La || !LLR || L < 1 || B < 1) return fail(TD_EINVAL, "td_siso_host: bad argument");
+    if (const int nf = not_fixed(h, "td_siso_host")) return nf;
     TD_HIP(hipSetDevice(h->p.device));
     int rc = h->p.precision == TD_F64 ? siso_host_t<double>(h, recs, La, terminated, LLR, L, B)
                                       : siso_host_t<float>(h, recs, La, terminated, LLR, L, B);
@@ -1404,7 +1528,10 @@ int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d
         return fail(TD_EHIP, "td_rate_dematch: this build has no td_ratematch.hip");
     TD_HIP(hipSetDevice(h->p.device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h->p.precision == TD_F64)
+    if (is_fixed(h)) {
+        if (!td::launch_fixed_dematch) return fail(TD_EHIP, "td_rate_dematch: this build has no td_fixed.hip");
+        TD_HIP(td::launch_fixed_dematch(p, static_cast<const int8_t*>(d_e), static_cast<int8_t*>(d_llr), accumulate, st));
+    } else if (h->p.precision == TD_F64)
         TD_HIP(td::launch_rate_dematch<double>(p, static_cast<const double*>(d_e), static_cast<double*>(d_llr), accumulate, st));
     else
         TD_HIP(td::launch_rate_dematch<float>(p, static_cast<const float*>(d_e), static_cast<float*>(d_llr), accumulate, st));

@@ -1,0 +1,52 @@
+// td_fixed.h -- launchers of the fixed-point decoder (TD_FIXED, td_fixed.hip) and its workspace carve.
+//
+// One lane decodes one codeword; every workspace array is [row][Bp] with the codeword as the fastest
+// index (Bp = B rounded up to kFxLanes), so that a wave's accesses to a row are contiguous.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "td_fixed_core.h"
+#include "td_ratematch.h"
+
+namespace td {
+
+constexpr int kFxLanes = 64;   // codewords of a wave = of a workgroup
+
+struct FxCarve {
+    size_t xs, xp1, xp2, ext12, ext21, ckpt, bitsT, total;
+    size_t Bp;
+};
+
+inline FxCarve fx_carve(int B, int K, int iters)
+{
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t L = (size_t)K + 3, Bp = ((size_t)B + kFxLanes - 1) / kFxLanes * kFxLanes;
+    const size_t nW = (L + fx::kW - 1) / fx::kW;
+    FxCarve c{};
+    c.Bp = Bp;
+    c.xs = 0;
+    c.xp1 = c.xs + up((L + 3) * Bp);
+    c.xp2 = c.xp1 + up(L * Bp);
+    c.ext12 = c.xp2 + up(L * Bp);
+    c.ext21 = c.ext12 + up((size_t)K * Bp * 2);
+    c.ckpt = c.ext21 + up((size_t)K * Bp * 2);
+    c.bitsT = c.ckpt + up(nW * 8 * Bp * 4);
+    c.total = c.bitsT + up((size_t)iters * K * Bp);   // a row per iteration (all_iters)
+    return c;
+}
+
+// Weak references, like td_ratematch.h's: a host-only link of td_api.cpp without td_fixed.hip still
+// links, and the fixed entry points then fail with TD_EHIP.  libturbo_mi355x.so always has them.
+// d_q [B][3K+12] int8 -> xs / xp1 / xp2 of the workspace (-128 read as -127, the padding zeroed)
+__attribute__((weak)) hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st);
+// all iterations of all codewords, then bitsT -> d_bits ([B][K] or [B][iters][K])
+__attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t st);
+// saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
+__attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
+                                                      int accumulate, hipStream_t st);
+
+}  // namespace td

@@ -1,0 +1,149 @@
+// td_fixed.hip -- the fixed-point decoder (TD_FIXED) on gfx950: int8 channel LLRs in, integer
+// Max-Log-MAP, int16 extrinsics, uint8 decisions.  The arithmetic is td_fixed_core.h's; here are the
+// kernels around it.
+//
+//   fx_demux_kernel    q [B][3K+12] -> xs, xp1, xp2 [row][Bp]: a 64 x 64 byte transpose through LDS, so
+//                      that both the reads (along the stream) and the writes (along the batch) are
+//                      contiguous; -128 becomes -127 and the lanes of the padding get zeros.
+//   fx_turbo_kernel    one codeword per lane, all iterations in one launch.  A lane keeps its eight
+//                      state metrics in registers (int32, never normalised); the forward pass leaves
+//                      alpha at every kW-th step in the workspace (32 B per kW steps and codeword), the
+//                      backward pass recomputes a window's alpha rows into registers and runs beta,
+//                      Lambda and the extrinsic over them.  The interleaver is a row index that the
+//                      whole wave shares, so every access to the workspace is one contiguous row piece.
+//   fx_bits_kernel     bitsT [rows][K][Bp] -> the caller's [B][rows][K], the transpose back.
+//   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
+#include <hip/hip_runtime.h>
+
+#include "td_fixed.h"
+
+namespace td {
+
+namespace {
+
+constexpr int kTile = 64;
+constexpr int kTileThreads = 256;
+
+__global__ __launch_bounds__(kTileThreads) void fx_demux_kernel(const int8_t* __restrict__ q, int K, int B, size_t Bp,
+                                                                 int8_t* __restrict__ xs, int8_t* __restrict__ xp1,
+                                                                 int8_t* __restrict__ xp2)
+{
+    __shared__ int8_t tile[kTile][kTile + 4];
+    const int n = 3 * K + 12, L = K + 3;
+    const int n0 = blockIdx.x * kTile;
+    const size_t b0 = (size_t)blockIdx.y * kTile;
+    const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
+    for (int r = ty; r < kTile; r += kTileThreads / kTile) {
+        int v = 0;
+        if (b0 + r < (size_t)B && n0 + tx < n) v = q[(b0 + r) * (size_t)n + n0 + tx];
+        tile[r][tx] = (int8_t)(v < -127 ? -127 : v);
+    }
+    __syncthreads();
+    for (int c = ty; c < kTile; c += kTileThreads / kTile) {
+        const int pos = n0 + c;
+        if (pos >= n) break;
+        int8_t* dst;
+        int row;
+        if (pos < 3 * K) {
+            row = pos / 3;
+            const int comp = pos - 3 * row;
+            dst = comp == 0 ? xs : comp == 1 ? xp1 : xp2;
+        } else {   // tails: (xs, xp) x 3 of the first encoder, then of the second (log_map.cpp:1119-1123)
+            const int t = pos - 3 * K, second = t >= 6, u = second ? t - 6 : t;
+            row = K + (u >> 1);
+            if (u & 1)
+                dst = second ? xp2 : xp1;
+            else {
+                dst = xs;
+                if (second) row = L + (u >> 1);
+            }
+        }
+        dst[(size_t)row * Bp + b0 + tx] = tile[tx][c];
+    }
+}
+
+__global__ __launch_bounds__(kFxLanes) void fx_turbo_kernel(fx::FxArgs p)
+{
+    fx::decode_codeword(p, blockIdx.x * kFxLanes + threadIdx.x);
+}
+
+__global__ __launch_bounds__(kTileThreads) void fx_bits_kernel(const uint8_t* __restrict__ bitsT, int K, int B, size_t Bp,
+                                                                int rows, uint8_t* __restrict__ bits)
+{
+    __shared__ uint8_t tile[kTile][kTile + 4];
+    const int k0 = blockIdx.x * kTile, row = blockIdx.z;
+    const size_t b0 = (size_t)blockIdx.y * kTile;
+    const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
+    for (int r = ty; r < kTile; r += kTileThreads / kTile)
+        tile[r][tx] = k0 + r < K ? bitsT[((size_t)row * K + k0 + r) * Bp + b0 + tx] : (uint8_t)0;
+    __syncthreads();
+    for (int c = ty; c < kTile; c += kTileThreads / kTile) {
+        const size_t b = b0 + c;
+        if (b < (size_t)B && k0 + tx < K) bits[(b * rows + row) * (size_t)K + k0 + tx] = tile[tx][c];
+    }
+}
+
+// The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
+// addition: no atomics, the same bytes on every run.
+template <bool ACC>
+__global__ __launch_bounds__(kTileThreads) void fx_dematch_kernel(RmParams p, const int8_t* __restrict__ e, int8_t* out)
+{
+    const int nout = 3 * p.K + 12;
+    const int q = blockIdx.x * kTileThreads + threadIdx.x;
+    if (q >= nout) return;
+    const int rk = p.rank[q];
+    int first = -1;
+    if (rk >= 0) first = rk >= p.c0 ? rk - p.c0 : rk - p.c0 + p.Nnn;
+    const bool sel = first >= 0 && first < p.E;
+    if (ACC && !sel) return;   // not selected: the soft buffer keeps its value
+    for (size_t b = blockIdx.y; b < (size_t)p.B; b += gridDim.y) {
+        int acc = 0;
+        if (ACC) {
+            acc = out[b * (size_t)nout + q];
+            acc = acc < -127 ? -127 : acc;
+        }
+        if (sel) {
+            const int8_t* eb = e + b * (size_t)p.E;
+            for (size_t k = (size_t)first; k < (size_t)p.E; k += (size_t)p.Nnn) {
+                acc += eb[k];
+                acc = acc > 127 ? 127 : acc < -127 ? -127 : acc;
+            }
+        }
+        out[b * (size_t)nout + q] = (int8_t)acc;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st)
+{
+    const int n = 3 * p.K + 12;
+    const dim3 grid((unsigned)((n + kTile - 1) / kTile), (unsigned)(p.Bp / kTile));
+    hipLaunchKernelGGL(fx_demux_kernel, grid, dim3(kTileThreads), 0, st, d_q, p.K, p.B, p.Bp,
+                       const_cast<int8_t*>(p.xs), const_cast<int8_t*>(p.xp1), const_cast<int8_t*>(p.xp2));
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t st)
+{
+    hipLaunchKernelGGL(fx_turbo_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int rows = p.all_iters ? p.iters : 1;
+    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
+    hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out, int accumulate, hipStream_t st)
+{
+    const int nout = 3 * p.K + 12;
+    const dim3 grid((unsigned)((nout + kTileThreads - 1) / kTileThreads), (unsigned)(p.B < 512 ? p.B : 512));
+    if (accumulate)
+        hipLaunchKernelGGL(fx_dematch_kernel<true>, grid, dim3(kTileThreads), 0, st, p, d_e, d_out);
+    else
+        hipLaunchKernelGGL(fx_dematch_kernel<false>, grid, dim3(kTileThreads), 0, st, p, d_e, d_out);
+    return hipGetLastError();
+}
+
+}  // namespace td

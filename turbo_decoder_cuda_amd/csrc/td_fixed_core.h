@@ -1,0 +1,212 @@
+// td_fixed_core.h -- the arithmetic of the fixed-point decoder (TD_FIXED), one codeword per caller.
+//
+// Plain integer C++ shared by the gfx950 kernel of td_fixed.hip (one codeword per lane) and by the
+// stand-alone host program of the tests (tests/fixed_core_host.cpp, under ASan + UBSan): the functions
+// only read and write through FxArgs, whose arrays are laid out [row][Bp] with the codeword as the
+// fastest index.  The library never decodes on the host.
+//
+// Metrics.  The branch metric is twice the float decoder's: gamma_u(s) = (2u-1) S + o_u(s) P with
+// S = xs + La, P = xp.  |xs|, |xp| <= 127 and |La| <= le_max <= 255, so |gamma| <= 509.  State metrics
+// are int32 and are never normalised: after i steps |alpha| <= 509 i <= 509 * 10003 < 2^23, the same
+// for beta, and |alpha + gamma + beta| < 2^24.  An unreachable state is kNeg = -2^28: sums of up to two
+// of them and a reachable part stay above -2^30, so nothing wraps, and no sum that contains one
+// reaches a reachable path's (>= -2^24).  Nothing saturates except the two clamps of the contract
+// (the input's -128 -> -127 and the extrinsic's +-le_max).
+#pragma once
+
+#include <stdint.h>
+#include <stddef.h>
+
+#if defined(__HIPCC__)
+#define TDF_HD __host__ __device__ __forceinline__
+#else
+#define TDF_HD inline
+#endif
+
+namespace td {
+namespace fx {
+
+constexpr int kW = 16;               // trellis steps per recomputation window (alpha rows held in registers)
+constexpr int kNeg = -(1 << 28);     // an unreachable state
+
+// The LTE constituent code (feedback 13, forward 15 octal) as gen_trellis builds it (td_tables.h
+// build_trellis): state s = (r0 r1 r2) with r0 the newest register bit in bit 2.
+constexpr int fb(int s, int u) { return u ^ ((s >> 1) & 1) ^ (s & 1); }                 // the register's input bit
+constexpr int next_state(int s, int u) { return (fb(s, u) << 2) | (s >> 1); }
+constexpr int parity(int s, int u) { return 2 * (fb(s, u) ^ ((s >> 2) & 1) ^ (s & 1)) - 1; }   // o_u(s) = +-1
+constexpr int prev_state(int j, int u) { return next_state(2 * (j & 3), u) == j ? 2 * (j & 3) : 2 * (j & 3) + 1; }
+
+struct FxArgs {
+    const int8_t* xs;     // [L+3][Bp] rows 0..L-1: systematic of SISO1 (natural order, tail included);
+                          //           rows L..L+2: the systematic tail of SISO2
+    const int8_t* xp1;    // [L][Bp]
+    const int8_t* xp2;    // [L][Bp]
+    int16_t* ext12;       // [K][Bp] Le of SISO1 by natural position
+    int16_t* ext21;       // [K][Bp] Le of SISO2 by interleaved position
+    int32_t* ckpt;        // [nW][8][Bp] alpha at the start of every window
+    uint8_t* bitsT;       // [rows][K][Bp] hard decisions by natural position
+    int16_t* le;          // nullable, the caller's [B][iters][2][L]
+    const int* pi;        // [K]
+    const int* pinv;      // [K]
+    int K, L, B, iters, all_iters;
+    int le_max, scale_q;
+    size_t Bp;            // codewords of the padded batch (the row pitch)
+};
+
+// f of the contract: towards zero, symmetric in sign, clamped
+TDF_HD int ext_f(int r, int le_max, int scale_q)
+{
+    int m = ((r < 0 ? -r : r) * scale_q) >> 2;
+    m = m < le_max ? m : le_max;
+    return r < 0 ? -m : m;
+}
+
+TDF_HD int imax(int a, int b) { return a > b ? a : b; }
+
+// An interleaver entry.  The tables do not change while a decode runs and the index is the same for
+// the whole wave, so the device reads them through the constant address space: a scalar load, whose
+// result (a row number) stays in a scalar register and makes the row's address a scalar too.
+TDF_HD int table_entry(const int* tbl, int i)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const int __attribute__((address_space(4))) * const_ptr;
+    return ((const_ptr)tbl)[i];
+#else
+    return tbl[i];
+#endif
+}
+
+// the four values a branch metric takes: index 2u + (o_u(s) > 0)
+TDF_HD void gammas(int S, int P, int (&c)[4])
+{
+    c[0] = -S - P;
+    c[1] = -S + P;
+    c[2] = S - P;
+    c[3] = S + P;
+}
+constexpr int gsel(int s, int u) { return 2 * u + (parity(s, u) > 0 ? 1 : 0); }
+
+TDF_HD void alpha_step(const int (&a)[8], int S, int P, int (&n)[8])
+{
+    int c[4];
+    gammas(S, P, c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int p0 = prev_state(j, 0), p1 = prev_state(j, 1);
+        n[j] = imax(a[p0] + c[gsel(p0, 0)], a[p1] + c[gsel(p1, 1)]);
+    }
+}
+
+// S = xs + La and P = xp of position i (i < L) of SISO `DEC` in iteration `it`
+template <int DEC>
+TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
+{
+    const int K = p.K;
+    if (DEC == 0) {
+        int la = 0;
+        if (it > 0 && i < K) la = p.ext21[(size_t)table_entry(p.pinv, i) * p.Bp + b];
+        S = p.xs[(size_t)i * p.Bp + b] + la;
+        P = p.xp1[(size_t)i * p.Bp + b];
+    } else {
+        int la = 0;
+        size_t row = (size_t)i + 3;   // tail: rows L .. L+2 = K+3 ..
+        if (i < K) {
+            row = (size_t)table_entry(p.pi, i);
+            la = p.ext12[row * p.Bp + b];
+        }
+        S = p.xs[row * p.Bp + b] + la;
+        P = p.xp2[(size_t)i * p.Bp + b];
+    }
+}
+
+// One terminated Max-Log-MAP pass of codeword b with everything that follows it in the iteration:
+// the extrinsic (ext12 / ext21 and the caller's Le), and after SISO2 the hard decisions.
+template <int DEC>
+TDF_HD void siso(const FxArgs& p, size_t b, int it)
+{
+    const int L = p.L, K = p.K;
+    const int nW = (L + kW - 1) / kW;
+    const bool live = b < (size_t)p.B;   // a lane of the padding decodes zeros and stores nothing outside the workspace
+
+    // forward: alpha at every window start
+    {
+        int a[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) a[s] = s ? kNeg : 0;
+        for (int w = 0; w < nW; ++w) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) p.ckpt[((size_t)w * 8 + s) * p.Bp + b] = a[s];
+            if (w == nW - 1) break;   // a window that is not the last is whole
+            int S[kW], P[kW];
+#pragma unroll
+            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, w * kW + t, S[t], P[t]);
+#pragma unroll
+            for (int t = 0; t < kW; ++t) {
+                int n[8];
+                alpha_step(a, S[t], P[t], n);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) a[s] = n[s];
+            }
+        }
+    }
+
+    // backward: per window, alpha again from its checkpoint, then beta and the outputs
+    int bt[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) bt[s] = s ? kNeg : 0;
+    const int row = p.all_iters ? it : 0;
+    const bool want_bits = DEC == 1 && (p.all_iters || it == p.iters - 1);
+    for (int w = nW - 1; w >= 0; --w) {
+        const int i0 = w * kW;
+        int S[kW], P[kW];
+#pragma unroll
+        for (int t = 0; t < kW; ++t) {
+            const int i = i0 + t < L ? i0 + t : L - 1;   // past the end (last window): a valid row, never used
+            load_step<DEC>(p, b, it, i, S[t], P[t]);
+        }
+        int A[kW][8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
+#pragma unroll
+        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1]);
+#pragma unroll
+        for (int t = kW - 1; t >= 0; --t) {
+            const int i = i0 + t;
+            if (i < L) {
+                int c[4];
+                gammas(S[t], P[t], c);
+                int e0[8], e1[8];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    e0[s] = c[gsel(s, 0)] + bt[next_state(s, 0)];
+                    e1[s] = c[gsel(s, 1)] + bt[next_state(s, 1)];
+                }
+                int m0 = A[t][0] + e0[0], m1 = A[t][0] + e1[0];
+#pragma unroll
+                for (int s = 1; s < 8; ++s) {
+                    m0 = imax(m0, A[t][s] + e0[s]);
+                    m1 = imax(m1, A[t][s] + e1[s]);
+                }
+                const int llr = (m1 - m0) >> 1;   // Lambda is even
+                const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
+                if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
+                if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
+                if (want_bits && i < K)
+                    p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+#pragma unroll
+                for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
+            }
+        }
+    }
+}
+
+TDF_HD void decode_codeword(const FxArgs& p, size_t b)
+{
+    for (int it = 0; it < p.iters; ++it) {
+        siso<0>(p, b, it);
+        siso<1>(p, b, it);
+    }
+}
+
+}  // namespace fx
+}  // namespace td

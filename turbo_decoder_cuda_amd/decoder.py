@@ -23,7 +23,8 @@ N_ITERATION = 15   # log_map.h:30
 TERMINATED = 1     # log_map.h:24
 
 _ALGOS = {"logmap": N.TD_ALGO_LOGMAP, "maxlog": N.TD_ALGO_MAXLOG}
-_PRECS = {"f64": N.TD_F64, "f32": N.TD_F32}
+_PRECS = {"f64": N.TD_F64, "f32": N.TD_F32, "fixed": N.TD_FIXED}
+_NP_DT = {"f64": np.float64, "f32": np.float32, "fixed": np.int8}
 _STOP_RULES = {None: N.TD_STOP_NONE, "hda": N.TD_STOP_HDA, "crc": N.TD_STOP_CRC}
 
 
@@ -39,7 +40,8 @@ class TurboCodec:
         self.L = self.K + 3
         self.iterations = int(iterations)
         self.algo, self.precision = algo, precision
-        self.dtype = np.float64 if precision == "f64" else np.float32
+        self.dtype = _NP_DT[precision]                                 # the channel LLRs
+        self.le_dtype = np.int16 if precision == "fixed" else self.dtype   # the extrinsics
         p = N.TdParams(self.K, self.f1, self.f2, self.iterations, _ALGOS[algo], _PRECS[precision], int(device))
         h = C.c_void_p()
         N.check(N.lib().td_create(C.byref(h), C.byref(p)))
@@ -93,6 +95,20 @@ class TurboCodec:
         v = C.c_ulonglong(0)
         N.check(N.lib().td_debug_workspace_bytes(self._h, C.byref(v)))
         return int(v.value)
+
+    def _torch_dtypes(self):
+        """(LLR dtype, Le dtype) of the device-resident calls."""
+        import torch
+
+        return {"f64": (torch.float64, torch.float64), "f32": (torch.float32, torch.float32),
+                "fixed": (torch.int8, torch.int16)}[self.precision]
+
+    def set_fixed(self, le_max: int = 255, ext_scale_q: int = 3) -> None:
+        """The fixed-point decoder's extrinsic (td_set_fixed; precision="fixed" only):
+        Le = clamp(sign(r) * ((|r| * ext_scale_q) >> 2), +-le_max), le_max in [1, 255], ext_scale_q in
+        [1, 4] quarters (4 = no scaling)."""
+        f = N.TdFixedParams(int(le_max), int(ext_scale_q))
+        N.check(N.lib().td_set_fixed(self._h, C.byref(f)))
 
     def set_window_maxstar(self, exact: bool) -> None:
         """max* of the windowed log-MAP schedule (td_set_window_maxstar): exact=False the one-read
@@ -149,7 +165,7 @@ class TurboCodec:
         flow = flow.reshape(-1, stream_length(self.K))
         B = flow.shape[0]
         out = np.zeros((B, self.iterations, self.K), dtype=np.int32)
-        le = np.zeros((B, self.iterations, 2, self.L), dtype=self.dtype) if return_le else None
+        le = np.zeros((B, self.iterations, 2, self.L), dtype=self.le_dtype) if return_le else None
         used = np.zeros(B, dtype=np.int32) if return_iters else None
         le_p = le.ctypes.data_as(C.c_void_p) if return_le else None
         if return_iters:
@@ -166,14 +182,15 @@ class TurboCodec:
 
     # -- device-resident decode (torch tensors as HBM buffers) ---------------------------
     def decode(self, llr, bits=None, all_iters: bool = False, le=None, stream=None, iters_out=None):
-        """llr: torch tensor [B, 3K+12] on this codec's device (float64 for f64, float32 for f32).
+        """llr: torch tensor [B, 3K+12] on this codec's device (float64 for f64, float32 for f32, int8
+        for fixed; le then int16).
         Returns uint8 bits [B, K] (or [B, iterations, K] with all_iters).  Asynchronous on
         `stream` (default: torch's current stream).  iters_out: None, an int32 [B] tensor that
         receives the iterations each codeword used, or True to have one made: the call then returns
         (bits, iters_out)."""
         import torch
 
-        want = torch.float64 if self.precision == "f64" else torch.float32
+        want, want_le = self._torch_dtypes()
         if llr.dtype != want or not llr.is_cuda or not llr.is_contiguous():
             raise ValueError(f"llr must be a contiguous {want} CUDA tensor")
         if llr.ndim != 2 or llr.shape[1] != stream_length(self.K):
@@ -187,7 +204,7 @@ class TurboCodec:
         else:
             self._check_out("bits", bits, torch.uint8, shape, llr.device)
         if le is not None:
-            self._check_out("le", le, want, (B, self.iterations, 2, self.L), llr.device)
+            self._check_out("le", le, want_le, (B, self.iterations, 2, self.L), llr.device)
         made = iters_out is True
         if made:
             iters_out = torch.empty((B,), dtype=torch.int32, device=llr.device)
@@ -251,12 +268,12 @@ class TurboCodec:
             raise ValueError(f"{name} is on {t.device}, the codec on cuda:{self.device}")
 
     def rate_match(self, x, rv: int, E: int, out=None, stream=None):
-        """x: uint8 / float32 / float64 tensor [B, 3K+12] on this codec's device (coded bits, or any
+        """x: uint8 / int8 / float32 / float64 tensor [B, 3K+12] on this codec's device (coded bits, or any
         per-position values) -> the E values a transmission of redundancy version rv carries,
         [B, E] of x's dtype: x[:, rate_match_index(K, Ncb, rv, E)].  After set_rate_matching."""
         import torch
 
-        self._check_in("x", x, (torch.uint8, torch.float32, torch.float64), stream_length(self.K))
+        self._check_in("x", x, (torch.uint8, torch.int8, torch.float32, torch.float64), stream_length(self.K))
         rv, E, B = int(rv), int(E), x.shape[0]
         if E < 1:
             raise ValueError(f"E must be at least 1, got {E}")
@@ -274,10 +291,11 @@ class TurboCodec:
         """e: the received soft values [B, E] of a transmission of redundancy version rv, in the codec's
         dtype -> LLRs [B, 3K+12] ready for decode: every position gets the sum of the e that were
         selected from it (repetition), punctured positions 0.  With accumulate the sums are added
-        into `out` (required then): HARQ combining of a retransmission into the soft buffer."""
+        into `out` (required then): HARQ combining of a retransmission into the soft buffer.  A fixed
+        codec takes and gives int8, and every addition saturates to [-127, 127]."""
         import torch
 
-        want = torch.float64 if self.precision == "f64" else torch.float32
+        want = self._torch_dtypes()[0]
         self._check_in("e", e, (want,))
         B, E = e.shape
         if E < 1:
@@ -368,6 +386,13 @@ class TurboCodec:
         N.check(N.lib().td_siso_host(self._h, recs2.ctypes.data_as(C.c_void_p), La2.ctypes.data_as(C.c_void_p),
                                      int(terminated), out.ctypes.data_as(C.c_void_p), L, B))
         return out[0] if one else out
+
+
+def quantise(llr, steps_per_unit: float):
+    """Float LLRs (a torch tensor) -> the int8 a fixed codec takes: round to nearest, clamp +-127."""
+    import torch
+
+    return torch.clamp(torch.round(llr * steps_per_unit), -127, 127).to(torch.int8)
 
 
 def modulate(bits, modulation: int, stream=None):
