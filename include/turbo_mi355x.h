@@ -239,14 +239,15 @@ int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table /* [K] */);
  * Max-Log-MAP decode of the same integers, bits and Le.
  * On a TD_FIXED handle td_decode_device / td_decode_device_stop / td_decode_host / td_decode_host_stop take
  * int8 LLRs [B][3K+12] (not modified) and give the bits as ever and d_le / le as int16
- * [B][iterations][2][K+3]; the _stop forms fill the counts with `iterations` (early termination of the
- * fixed decoder does not exist yet).  Asynchronous, one workspace, event ordering and capture as
+ * [B][iterations][2][K+3]; the _stop forms fill the counts with `iterations` unless a rule is set
+ * (td_set_fixed_stop below: the fixed decoder's early termination).  Asynchronous, one workspace, event ordering and capture as
  * documented at td_decode_device.  td_reserve sizes the workspace with a plain allocation (no placement
  * search); after it a decode allocates nothing and may be captured into a hipGraph.  td_profile_read
  * reports the demultiplex (the transpose of the int8 stream into the workspace) and the decode.
  * td_rate_dematch takes int8 d_e and int8 d_llr (see there); td_rate_match with elem_size 1 moves int8.
  * TD_EINVAL on a TD_FIXED handle, never silently ignored: td_set_window, td_set_window_maxstar,
- * td_set_early_stop, td_set_window_stop, td_siso_host, td_clock_read, td_debug_set_stamps.
+ * td_set_early_stop, td_set_window_stop, td_siso_host, td_clock_read, td_debug_set_stamps.  The other
+ * way round, td_set_fixed and td_set_fixed_stop are TD_EINVAL on a handle of another precision.
  *
  * td_set_fixed: le_max in [1, 255], ext_scale_q in [1, 4] (quarters; 4 = no scaling); the default is
  * {255, 3}, which NULL restores.  TD_EINVAL on a handle of another precision or a value out of range; a
@@ -257,6 +258,33 @@ typedef struct td_fixed_params {
     int ext_scale_q;   /* the extrinsic's scale in quarters */
 } td_fixed_params;
 int td_set_fixed(td_handle* h, const td_fixed_params* f);
+/*
+ * Per-codeword early termination of the fixed-point decoder: the third sibling of td_set_early_stop and
+ * td_set_window_stop, with their two rules, td_stop_params, frozen-row convention and iters_used output,
+ * judged on the fixed decode's own rows.  Off by default; with it off a fixed decode launches the
+ * kernels it always did.
+ *   row(n)  the hard-decision row after n iterations of the full fixed decode with the handle's
+ *           td_set_fixed setting (row n-1 of an all_iters decode with the rule off).
+ *   TD_STOP_HDA  codeword b stops after the smallest n >= max(2, min_iters) with row(n) == row(n-1) on
+ *                all K bits; without such an n, at `iterations`.
+ *   TD_STOP_CRC  after the smallest n >= max(1, min_iters) with CRC-24(row(n)) == 0 (the polynomial
+ *                convention of td_set_early_stop and td_crc24_host).  Needs K > 24.
+ * iters_used[b] = n and the decoded bits of b are row(n).  With all_iters, rows <= n equal the full
+ * decode's and rows n+1 .. iterations are copies of row(n).  d_le entries of iterations <= n equal the
+ * full decode's; later entries are unspecified (the decoder does not write them).  A codeword's result
+ * does not depend on its wave of 64, its batch or the batch size: a stopped codeword's lane is skipped
+ * while its wave's other codewords go on, and a wave returns once all of its codewords have stopped
+ * (which is where time can be saved).  min_iters == iterations reproduces the full decode byte for byte.
+ * Valid only on a TD_FIXED handle: otherwise TD_EINVAL.  Argument checks as td_set_early_stop
+ * (TD_EINVAL: unknown rule, min_iters outside [1, iterations], TD_STOP_CRC with crc_poly == 0 or
+ * K <= 24); a failed call leaves the previous setting in place.  NULL or rule TD_STOP_NONE turns the
+ * rule off.  The rule survives td_set_fixed.  The CRC rule's device table (td_crc24_syndromes) is built
+ * here, and the per-codeword counts live in the workspace that td_reserve sizes (whether or not a rule
+ * is set), so after td_reserve a decode allocates nothing and may be captured into a hipGraph.
+ * td_decode_device_stop / td_decode_host_stop fill the counts; the plain entry points behave like them
+ * with a null count pointer.
+ */
+int td_set_fixed_stop(td_handle* h, const td_stop_params* s);
 
 /* Kernel timing (measurement support): while enabled, hipEvents on the decode stream bracket
  * the demultiplex kernel and the turbo kernel of every td_decode_device call.

@@ -111,7 +111,8 @@ struct td_handle {
     // early termination (td_set_early_stop): rule 0 = off
     td_stop_params stop{TD_STOP_NONE, 1, 0};
     uint32_t* d_crc = nullptr;      // [K] CRC syndromes by natural bit position (td_crc.h), built by td_set_early_stop
-                                    // or td_set_window_stop (a handle has a rule of one kind at most)
+                                    // or td_set_window_stop (a handle has a rule of one kind at most); a fixed
+                                    // handle's are td_set_fixed_stop's, by interleaved position
     // early termination of the windowed schedule (td_set_window_stop): rule 0 = off
     td_stop_params wstop{TD_STOP_NONE, 1, 0};
     bool clk_stopped = false;       // the last decode ran the stopping windowed kernels (no clock sample)
@@ -126,6 +127,8 @@ struct td_handle {
     bool rm_set = false;
     // the fixed-point decoder (TD_FIXED): the extrinsic's clamp and scale (td_set_fixed)
     td_fixed_params fxp{255, 3};
+    // early termination of the fixed-point decoder (td_set_fixed_stop): rule 0 = off; its CRC table is d_crc
+    td_stop_params fstop{TD_STOP_NONE, 1, 0};
 };
 
 namespace td {
@@ -666,7 +669,7 @@ int ensure_fixed_ws(td_handle* h, int B)
 int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le, int32_t* d_iters,
                  hipStream_t st)
 {
-    if (!td::launch_fixed_demux || !td::launch_fixed_turbo)
+    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop)
         return fail(TD_EHIP, "td_decode_device: this build has no td_fixed.hip");
     int rc = ensure_fixed_ws(h, B);
     if (rc) return rc;
@@ -711,9 +714,19 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
     hipError_t e = td::launch_fixed_demux(a, static_cast<const int8_t*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
-    e = td::launch_fixed_turbo(a, d_bits, st);
-    if (e == hipSuccess && d_iters)   // no early termination in fixed point: every codeword takes them all
-        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
+    if (h->fstop.rule != TD_STOP_NONE) {
+        const bool hda = h->fstop.rule == TD_STOP_HDA;
+        td::fx::FxStop s{};
+        s.rule = h->fstop.rule;
+        s.first = std::max(hda ? 2 : 1, h->fstop.min_iters);
+        s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
+        s.used = reinterpret_cast<int32_t*>(ws + c.used);
+        e = td::launch_fixed_turbo_stop(a, s, d_bits, d_iters, st);
+    } else {
+        e = td::launch_fixed_turbo(a, d_bits, st);
+        if (e == hipSuccess && d_iters)   // no rule (td_set_fixed_stop): every codeword takes them all
+            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
+    }
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_turbo");
     h->clk_valid = false;
     if (ev) {
@@ -1115,6 +1128,37 @@ int td_set_window_stop(td_handle* h, const td_stop_params* s)
         TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     h->wstop = *s;
+    return TD_OK;
+}
+
+int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed_stop: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_stop: the handle is not fixed-point (TD_FIXED)");
+    if (!s || s->rule == TD_STOP_NONE) {
+        h->fstop = td_stop_params{TD_STOP_NONE, 1, 0};
+        return TD_OK;
+    }
+    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_fixed_stop: unknown rule");
+    if (s->min_iters < 1 || s->min_iters > h->p.iterations)
+        return fail(TD_EINVAL, "td_set_fixed_stop: min_iters must be in [1, iterations]");
+    if (s->rule == TD_STOP_CRC) {
+        if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
+            return fail(TD_EINVAL, "td_set_fixed_stop: crc_poly must be the 24 low-order coefficients, non-zero");
+        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_fixed_stop: TD_STOP_CRC needs K > 24");
+        TD_HIP(hipSetDevice(h->p.device));
+        // the table lives on the device from here on: a decode allocates nothing for the rule
+        if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
+            h->d_crc = nullptr;
+            return fail(TD_ENOMEM, "td_set_fixed_stop: hipMalloc failed");
+        }
+        std::vector<uint32_t> syn((size_t)h->p.K), tab((size_t)h->p.K);
+        td::crc24_syndromes(h->p.K, s->crc_poly, syn.data());
+        for (int i = 0; i < h->p.K; ++i) tab[i] = syn[h->pi[i]];   // in the order SISO2 meets the bits (FxStop)
+        TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
+        TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    h->fstop = *s;
     return TD_OK;
 }
 

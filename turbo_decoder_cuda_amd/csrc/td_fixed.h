@@ -17,7 +17,7 @@ namespace td {
 constexpr int kFxLanes = 64;   // codewords of a wave = of a workgroup
 
 struct FxCarve {
-    size_t xs, xp1, xp2, ext12, ext21, ckpt, bitsT, total;
+    size_t xs, xp1, xp2, ext12, ext21, ckpt, bitsT, used, total;
     size_t Bp;
 };
 
@@ -35,7 +35,8 @@ inline FxCarve fx_carve(int B, int K, int iters)
     c.ext21 = c.ext12 + up((size_t)K * Bp * 2);
     c.ckpt = c.ext21 + up((size_t)K * Bp * 2);
     c.bitsT = c.ckpt + up(nW * 8 * Bp * 4);
-    c.total = c.bitsT + up((size_t)iters * K * Bp);   // a row per iteration (all_iters)
+    c.used = c.bitsT + up((size_t)iters * K * Bp);   // a row per iteration (all_iters, early termination)
+    c.total = c.used + up(Bp * 4);                   // int32 [Bp]: iterations used (td_set_fixed_stop), always carved
     return c;
 }
 
@@ -45,6 +46,10 @@ inline FxCarve fx_carve(int B, int K, int iters)
 __attribute__((weak)) hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st);
 // all iterations of all codewords, then bitsT -> d_bits ([B][K] or [B][iters][K])
 __attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t st);
+// the same with early termination: a codeword's rows past its stop are copies of its stop row, d_bits
+// without all_iters is its stop row, and d_iters (nullable, [B]) gets s.used
+__attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uint8_t* d_bits,
+                                                         int32_t* d_iters, hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

@@ -12,6 +12,10 @@
 //                      Lambda and the extrinsic over them.  The interleaver is a row index that the
 //                      whole wave shares, so every access to the workspace is one contiguous row piece.
 //   fx_bits_kernel     bitsT [rows][K][Bp] -> the caller's [B][rows][K], the transpose back.
+//   fx_turbo_stop_kernel, fx_bits_stop_kernel  the same two with early termination (td_set_fixed_stop): a
+//                      lane whose codeword has stopped is skipped, a wave whose lanes have all stopped
+//                      returns, and the transpose back reads row min(row, used - 1) and undoes the interleaved
+//                      order that the stopping decoder keeps its decisions in.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
 #include <hip/hip_runtime.h>
 
@@ -83,6 +87,41 @@ __global__ __launch_bounds__(kTileThreads) void fx_bits_kernel(const uint8_t* __
     }
 }
 
+// The stopping decoder (td_set_fixed_stop): a wave ends once its 64 codewords have stopped.
+__global__ __launch_bounds__(kFxLanes) void fx_turbo_stop_kernel(fx::FxArgs p, fx::FxStop s)
+{
+    fx::decode_codeword_stop(p, s, blockIdx.x * kFxLanes + threadIdx.x);
+}
+
+// fx_bits_kernel after a stopping decode: bitsT holds rows 0 .. used[b] - 1 of codeword b by interleaved
+// position, and output row r is row min(r, used[b] - 1) -- the frozen rows -- or, without all_iters
+// (rows == 1), the stop row.  Natural position k is workspace row pinv[k]: still one contiguous piece.
+__global__ __launch_bounds__(kTileThreads) void fx_bits_stop_kernel(const uint8_t* __restrict__ bitsT,
+                                                                     const int32_t* __restrict__ used,
+                                                                     const int* __restrict__ pinv, int K, int B,
+                                                                     size_t Bp, int rows, int iters,
+                                                                     uint8_t* __restrict__ bits, int32_t* __restrict__ d_iters)
+{
+    __shared__ uint8_t tile[kTile][kTile + 4];
+    const int k0 = blockIdx.x * kTile, row = blockIdx.z;
+    const size_t b0 = (size_t)blockIdx.y * kTile;
+    const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
+    int n = iters;   // a lane of the padding has no rows: any row inside the workspace
+    if (b0 + tx < (size_t)B) {
+        n = used[b0 + tx];
+        n = n < 1 ? 1 : n > iters ? iters : n;
+        if (d_iters && blockIdx.x == 0 && row == 0 && ty == 0) d_iters[b0 + tx] = n;
+    }
+    const int src = rows == 1 ? n - 1 : row < n - 1 ? row : n - 1;
+    for (int r = ty; r < kTile; r += kTileThreads / kTile)
+        tile[r][tx] = k0 + r < K ? bitsT[((size_t)src * K + pinv[k0 + r]) * Bp + b0 + tx] : (uint8_t)0;
+    __syncthreads();
+    for (int c = ty; c < kTile; c += kTileThreads / kTile) {
+        const size_t b = b0 + c;
+        if (b < (size_t)B && k0 + tx < K) bits[(b * rows + row) * (size_t)K + k0 + tx] = tile[tx][c];
+    }
+}
+
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
 // addition: no atomics, the same bytes on every run.
 template <bool ACC>
@@ -132,6 +171,19 @@ hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t 
     const int rows = p.all_iters ? p.iters : 1;
     const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
     hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uint8_t* d_bits, int32_t* d_iters,
+                                   hipStream_t st)
+{
+    hipLaunchKernelGGL(fx_turbo_stop_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int rows = p.all_iters ? p.iters : 1;
+    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
+    hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s.used, p.pinv, p.K, p.B, p.Bp,
+                       rows, p.iters, d_bits, d_iters);
     return hipGetLastError();
 }
 

@@ -44,13 +44,24 @@ struct FxArgs {
     int16_t* ext12;       // [K][Bp] Le of SISO1 by natural position
     int16_t* ext21;       // [K][Bp] Le of SISO2 by interleaved position
     int32_t* ckpt;        // [nW][8][Bp] alpha at the start of every window
-    uint8_t* bitsT;       // [rows][K][Bp] hard decisions by natural position
+    uint8_t* bitsT;       // [rows][K][Bp] hard decisions by natural position (the stopping decoder: by interleaved
+                          //                 position, a row per iteration)
     int16_t* le;          // nullable, the caller's [B][iters][2][L]
     const int* pi;        // [K]
     const int* pinv;      // [K]
     int K, L, B, iters, all_iters;
     int le_max, scale_q;
     size_t Bp;            // codewords of the padded batch (the row pitch)
+};
+
+// Early termination (td_set_fixed_stop), next to FxArgs and not in it: tests/fixed_core_host.cpp
+// initialises FxArgs member by member.
+struct FxStop {
+    int rule;             // 1: the rows repeat (HDA), 2: the row's CRC-24 is zero (enum td_stop_rule)
+    int first;            // the smallest iteration count a codeword may stop after: max(HDA ? 2 : 1, min_iters)
+    const int* syn;       // [K] CRC, by interleaved position i: the remainder of the row with only bit pi(i) set
+                          //     (td_crc.h's syndrome[pi[i]]), as bit patterns
+    int32_t* used;        // [Bp] the iterations each codeword took
 };
 
 // f of the contract: towards zero, symmetric in sign, clamped
@@ -121,8 +132,19 @@ TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
 
 // One terminated Max-Log-MAP pass of codeword b with everything that follows it in the iteration:
 // the extrinsic (ext12 / ext21 and the caller's Le), and after SISO2 the hard decisions.
-template <int DEC>
-TDF_HD void siso(const FxArgs& p, size_t b, int it)
+//
+// STOP (the stopping decoder, sp its rule): SISO2 writes row `it` of bitsT in every iteration and returns
+// the rule's evidence on it, zero where the codeword may stop.  Both rules hold in any fixed order of
+// the bits, so the stopping decoder keeps bitsT in SISO2's own order, by interleaved position i: the
+// stores and the rule need no entry of pi (a scalar load and its wait in every step otherwise), and
+// the transpose back undoes the order (fx_bits_stop_kernel reads row pinv[k]).  HDA: the window's bits
+// of row it - 1 are loaded with the window's inputs -- sixteen loads in flight ahead of the
+// arithmetic, not one per step behind a store that the compiler must assume aliases it -- packed one
+// bit a step into a register, and compared with the window's new bits at its end.  CRC: the lane XORs
+// in the syndrome of every 1 bit, from a table in the same order.  The state is the evidence and two
+// bit masks; the previous row stays in the workspace.  Iterations before sp->first are not judged.
+template <int DEC, bool STOP>
+TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
 {
     const int L = p.L, K = p.K;
     const int nW = (L + kW - 1) / kW;
@@ -154,8 +176,10 @@ TDF_HD void siso(const FxArgs& p, size_t b, int it)
     int bt[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) bt[s] = s ? kNeg : 0;
-    const int row = p.all_iters ? it : 0;
-    const bool want_bits = DEC == 1 && (p.all_iters || it == p.iters - 1);
+    const int row = STOP || p.all_iters ? it : 0;
+    const bool want_bits = DEC == 1 && (STOP || p.all_iters || it == p.iters - 1);
+    const bool judge = STOP && DEC == 1 && it + 1 >= sp->first;
+    int acc = 0;
     for (int w = nW - 1; w >= 0; --w) {
         const int i0 = w * kW;
         int S[kW], P[kW];
@@ -163,6 +187,17 @@ TDF_HD void siso(const FxArgs& p, size_t b, int it)
         for (int t = 0; t < kW; ++t) {
             const int i = i0 + t < L ? i0 + t : L - 1;   // past the end (last window): a valid row, never used
             load_step<DEC>(p, b, it, i, S[t], P[t]);
+        }
+        unsigned was = 0, now = 0;   // HDA: bit t = the bit of position i0 + t in row it - 1, in row it
+        if (STOP && judge && sp->rule == 1) {
+            const uint8_t* prev = p.bitsT + (size_t)(row - 1) * K * p.Bp + b;   // first >= 2: row it - 1 exists
+#pragma unroll
+            for (int t = 0; t < kW; ++t) {   // no branch per step: sixteen loads in flight, the tail's masked off
+                const int i = i0 + t < K ? i0 + t : K - 1;
+                was |= (unsigned)prev[(size_t)i * p.Bp] << t;
+            }
+            const int nv = K - i0;   // the window's positions below K
+            was &= nv >= kW ? (1u << kW) - 1 : nv > 0 ? (1u << nv) - 1 : 0u;
         }
         int A[kW][8];
 #pragma unroll
@@ -191,13 +226,32 @@ TDF_HD void siso(const FxArgs& p, size_t b, int it)
                 const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
                 if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
                 if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
-                if (want_bits && i < K)
-                    p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+                if (!STOP) {
+                    if (want_bits && i < K)
+                        p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+                } else if (want_bits && i < K) {
+                    const int bit = llr < 0 ? 0 : 1;
+                    p.bitsT[((size_t)row * K + (size_t)i) * p.Bp + b] = (uint8_t)bit;
+                    if (judge) {
+                        if (sp->rule == 1)
+                            now |= (unsigned)bit << t;
+                        else
+                            acc ^= -bit & table_entry(sp->syn, i);
+                    }
+                }
 #pragma unroll
                 for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
             }
         }
+        acc |= (int)(was ^ now);
     }
+    return acc;
+}
+
+template <int DEC>
+TDF_HD void siso(const FxArgs& p, size_t b, int it)
+{
+    siso_pass<DEC, false>(p, nullptr, b, it);
 }
 
 TDF_HD void decode_codeword(const FxArgs& p, size_t b)
@@ -206,6 +260,40 @@ TDF_HD void decode_codeword(const FxArgs& p, size_t b)
         siso<0>(p, b, it);
         siso<1>(p, b, it);
     }
+}
+
+// true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
+TDF_HD bool any_lane(bool run)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(run) != 0;
+#else
+    return run;
+#endif
+}
+
+// decode_codeword with early termination.  Codeword b stops after the first judged iteration whose
+// evidence is zero, else after p.iters; from then on its lane is skipped by a branch and writes
+// nothing more: bitsT holds rows 0 .. used - 1, and the rows a caller sees beyond them are the copies
+// that the transpose back makes (fx_bits_stop_kernel).  The loop's exit is the wave's: it leaves once
+// none of its lanes runs, so `it` and every table index stay uniform.  A lane of the padding never
+// runs (its zeros decode to an all-ones row, which no CRC passes).
+TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b)
+{
+    bool run = b < (size_t)p.B;
+    int used = p.iters;
+    for (int it = 0; it < p.iters; ++it) {
+        if (run) {
+            siso_pass<0, true>(p, &s, b, it);
+            const int acc = siso_pass<1, true>(p, &s, b, it);
+            if (it + 1 >= s.first && acc == 0) {
+                used = it + 1;
+                run = false;
+            }
+        }
+        if (!any_lane(run)) break;
+    }
+    s.used[b] = used;
 }
 
 }  // namespace fx

@@ -47,7 +47,7 @@ class TurboCodec:
         N.check(N.lib().td_create(C.byref(h), C.byref(p)))
         self._h = h
         self.device = int(device)
-        self.early_stop = None   # set_early_stop / set_window_early_stop
+        self.early_stop = None   # set_early_stop / set_window_early_stop / set_fixed_early_stop
         self._window_stop = False   # the rule in self.early_stop is the windowed schedule's
 
     # -- lifetime (TurboCodingRelease) -------------------------------------------------
@@ -149,6 +149,16 @@ class TurboCodec:
         self.early_stop = rule
         self._window_stop = rule is not None
 
+    def set_fixed_early_stop(self, rule=None, min_iters: int = 1, crc_poly: int = N.CRC24B) -> None:
+        """Per-codeword early termination of the fixed-point decoder (td_set_fixed_stop; precision="fixed"
+        only): the rules, arguments and frozen-row convention of set_early_stop, judged on the fixed
+        decode's own rows.  The rule survives set_fixed."""
+        if rule not in _STOP_RULES:
+            raise ValueError(f"rule must be 'hda', 'crc' or None, got {rule!r}")
+        s = N.TdStopParams(_STOP_RULES[rule], int(min_iters), int(crc_poly) & 0xFFFFFFFF)
+        N.check(N.lib().td_set_fixed_stop(self._h, C.byref(s)))
+        self.early_stop = rule
+
     def debug_window_layout(self, run: int = 0, run_a: int = 0, parts: int = 0) -> None:
         """Windowed kernels' layout for tests and measurements (td_debug_window_layout): sub-blocks
         per lane run (beta and alpha kernels) and batch parts; 0 = the layout's own choice."""
@@ -158,8 +168,8 @@ class TurboCodec:
     def TurboDecoding(self, flow: np.ndarray, return_le: bool = False, return_iters: bool = False):
         """flow [B, 3K+12] (or one row) -> out int32 [B, iterations, K] (the reference's
         flow_decoded rows); with return_le also Le [B, iterations, 2, K+3]; with return_iters also
-        the iterations each codeword used, int32 [B] (all `iterations` unless set_early_stop or
-        set_window_early_stop)."""
+        the iterations each codeword used, int32 [B] (all `iterations` unless set_early_stop,
+        set_window_early_stop or set_fixed_early_stop)."""
         flow = np.ascontiguousarray(flow, dtype=self.dtype)
         one = flow.ndim == 1
         flow = flow.reshape(-1, stream_length(self.K))
