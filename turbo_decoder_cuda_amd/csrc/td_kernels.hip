@@ -1111,7 +1111,7 @@ __device__ __forceinline__ void astore_row(T* sa, unsigned voff, T v)
 // UNnormalised difference fl(fl(g_p + an) - fl(g_s + a)), which is known before the tempmax tree,
 // so the table read (60-70 cycles) overlaps the tree's three (DPP, max) levels and the exact
 // difference's sub / fma / sub instead of following them.  The exact difference d is formed as
-// before and only its bucket is compared with the speculated one (OR-ed into `miss`); the
+// before and only its bucket is compared with the speculated one (spec_check, into `miss`); the
 // threshold compare, the select and the add use d itself, so a step whose buckets agree is
 // bit-identical to the committed order.  A window with any mismatch in any lane is recomputed in
 // the committed order from its first alpha (alpha_window), stores included, before the barrier:
@@ -1129,11 +1129,29 @@ __device__ __forceinline__ void astore_row(T* sa, unsigned voff, T v)
 template <typename T, int ALGO>
 constexpr bool kASpec = ALGO == 0 && kW == 15;
 
+// The speculation's bucket check of one step: the bucket of the exact difference d (x) against the
+// speculated one q, accumulated in a VGPR (left to itself the compiler turns a boolean flag into 15
+// compares and SALU ORs of VCC at the window's end, on the chain's tail).  The xor of two clamped
+// bucket fields is below 2^13 and a window adds kW of them, so the sum is non-zero exactly when some
+// step's buckets differed: one xor-add where xor and or had been two operations.  A step hands its
+// (d, q) to the next one (SpecPend), which issues the check inside its tempmax tree: config 2 -0.7 to
+// -1.7 % kernel time on two boxes; the xor-add issued in the old place measured level
+// (profiles/step_trim/ab_variants.txt).
+template <typename T>
+struct SpecPend {
+    T d;     // the step's exact difference
+    int q;   // the bucket its table row was read from
+};
+__device__ __forceinline__ void spec_check(unsigned& miss, unsigned x, int q)
+{
+    asm("v_xad_u32 %0, %1, %2, %0" : "+v"(miss) : "v"(x), "v"(q));   // miss += x ^ q
+}
+
 template <typename T, int ALGO, int K>
 struct AlphaSchedS {
     static __device__ __forceinline__ void run(T& a, StepIn<T> (&op)[3], const Smem<T>& sm, int tb, const T* lut,
                                                int c, const LaneConst<T>& lc, T* sa, T* stm, const unsigned (&va)[3],
-                                               TmBatch<T>& tbh, unsigned& miss)
+                                               TmBatch<T>& tbh, unsigned& miss, SpecPend<T>& sp)
     {
         constexpr int PH = K % 3;
         const StepIn<T> in = op[K % 3];
@@ -1150,18 +1168,25 @@ struct AlphaSchedS {
             astore_row<T, K>(sa, va[PH], a);   // alpha_raw[.][i]
             __builtin_amdgcn_sched_barrier(0);
             T m = vmax(a, an);                                   // tempmax[i] (:986-993), alpha_tempmax's tree
+            // The previous step's bucket check, off the chain, issued inside this step's tree: its bit
+            // field and clamp fill the two wait states between the first max and the DPP moves that
+            // read it, its xor-add one of the two behind the second max (both were s_nop).  Issued
+            // behind its own step's difference, as before, the check sat between the step's last add
+            // and the next partner exchange.
+            [[maybe_unused]] unsigned x = 0;
+            if constexpr (K > 0) x = (unsigned)bucket_dev<T>(sp.d);
             m = vmax(m, dpp<PhaseDpp<(PH + 1) % 3>::ctrl>(m));
+            if constexpr (K > 0) spec_check(miss, x, sp.q);
             m = vmax(m, dpp<PhaseDpp<(PH + 2) % 3>::ctrl>(m));
             const T alpha = a - m, ap = an - m;                  // :995-1000
             const T xs = fma(lc.a_sg[PH], in.gs, alpha);
             const T xp = fma(lc.a_pg[PH], in.gp, ap);
             const T d = xp - xs;
-            // per step, in a VGPR (left to itself the compiler turns the flag into 15 compares and
-            // SALU ORs of VCC at the window's end, on the chain's tail)
-            unsigned x = (unsigned)bucket_dev<T>(d);
-            asm("v_xor_b32 %1, %1, %2\n\tv_or_b32 %0, %0, %1" : "+v"(miss), "+v"(x) : "v"(qr));
+            sp.d = d;
+            sp.q = qr;
             a = sched_finish(xs, xp, d, thr, lo, hi);
-            AlphaSchedS<T, ALGO, K + 1>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss);
+            if constexpr (K == kW - 1) spec_check(miss, (unsigned)bucket_dev<T>(d), qr);   // the window's last step
+            AlphaSchedS<T, ALGO, K + 1>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss, sp);
             return;
         }
         T an;                                         // partner's alpha_raw
@@ -1191,13 +1216,14 @@ struct AlphaSchedS {
             __builtin_amdgcn_sched_barrier(0);
             a = vmax(xs, xp);
         }
-        AlphaSchedS<T, ALGO, K + 1>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss);
+        AlphaSchedS<T, ALGO, K + 1>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss, sp);
     }
 };
 template <typename T, int ALGO>
 struct AlphaSchedS<T, ALGO, kW> {
     static __device__ __forceinline__ void run(T&, StepIn<T> (&)[3], const Smem<T>&, int, const T*, int,
-                                               const LaneConst<T>&, T*, T*, const unsigned (&)[3], TmBatch<T>&, unsigned&)
+                                               const LaneConst<T>&, T*, T*, const unsigned (&)[3], TmBatch<T>&, unsigned&,
+                                               SpecPend<T>&)
     {
     }
 };
@@ -1850,7 +1876,8 @@ __device__ void siso_wg(Smem<T>& sm, const SisoSrc<T>& src, const SisoDst<T>& ds
                     TD_CHAIN_T0(c0);
                     const T a0 = a;
                     unsigned miss = 0;
-                    AlphaSchedS<T, ALGO, 0>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss);
+                    SpecPend<T> sp{(T)0, 0};
+                    AlphaSchedS<T, ALGO, 0>::run(a, op, sm, tb, lut, c, lc, sa, stm, va, tbh, miss, sp);
                     if constexpr (kASpec<T, ALGO>) {
 #ifdef TD_ASPEC_REDO
                         miss = 1;
