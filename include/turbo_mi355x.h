@@ -247,7 +247,8 @@ int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table /* [K] */);
  * td_rate_dematch takes int8 d_e and int8 d_llr (see there); td_rate_match with elem_size 1 moves int8.
  * TD_EINVAL on a TD_FIXED handle, never silently ignored: td_set_window, td_set_window_maxstar,
  * td_set_early_stop, td_set_window_stop, td_siso_host, td_clock_read, td_debug_set_stamps.  The other
- * way round, td_set_fixed and td_set_fixed_stop are TD_EINVAL on a handle of another precision.
+ * way round, td_set_fixed, td_set_fixed_stop and td_set_fixed_window are TD_EINVAL on a handle of another
+ * precision.
  *
  * td_set_fixed: le_max in [1, 255], ext_scale_q in [1, 4] (quarters; 4 = no scaling); the default is
  * {255, 3}, which NULL restores.  TD_EINVAL on a handle of another precision or a value out of range; a
@@ -285,6 +286,48 @@ int td_set_fixed(td_handle* h, const td_fixed_params* f);
  * with a null count pointer.
  */
 int td_set_fixed_stop(td_handle* h, const td_stop_params* s);
+/*
+ * The fixed-point decoder's sub-block schedule: the integer form of td_set_window's geometry, for
+ * batches too small to fill the chip with one lane a codeword.  Off by default (the exact full-trellis
+ * schedule above, whose kernels do not change); NULL or window == 0 restores it.  Otherwise window (W)
+ * is a multiple of 16, >= 16, and 0 <= overlap <= 3 W.  With L = K + 3 and nS = max(1, L / W) (integer
+ * division) each SISO pass of the TD_FIXED contract above becomes nS independent passes:
+ *   sub-block s   covers the positions [s W, (s+1) W); the last one, s = nS - 1, runs up to L (it takes the
+ *                 remainder and the tail: up to 2 W - 1 + 3 positions).  Call its end e.
+ *   alpha         starts at position max(s W - overlap, 0): from the terminated state (state 0 = 0, the
+ *                 others unreachable) if s W - overlap <= 0, else from equal metrics (all states 0).
+ *   beta          starts at position min(e + overlap, L): from the terminated state if e + overlap >= L,
+ *                 else from equal metrics.
+ *   warm-up       the steps outside [s W, e) only carry the recursions; they produce no output.
+ *   output        Lambda, LLR = Lambda >> 1 (Lambda stays even), Le = f(LLR - La - xs) with the handle's
+ *                 td_set_fixed setting and the hard bit at the sub-block's own positions, from its own
+ *                 alpha and beta: exactly the TD_FIXED contract's branch metric, plain max and f.
+ * The iteration (SISO1 over all sub-blocks, then SISO2 over all sub-blocks, serially), the hard decision
+ * and the layouts of d_bits and d_le are the TD_FIXED contract's.  No next-iteration initialisation, no
+ * concurrent SISOs and no extra extrinsic scale (td_window_params' nii, concurrent, ext_scale have no
+ * counterpart here).  The state metrics are wide enough that nothing saturates but the contract's two
+ * clamps; the result is the one that un-normalised integers of unlimited width give (max-log does not
+ * change when a constant is added to all states, so an implementation may normalise or not).  Every
+ * value is therefore defined bit for bit (tests/fixed_window_ref.py restates it).
+ * Consequences: with overlap >= L, or window > L/2 (nS = 1), the decode equals the exact fixed decode
+ * bit for bit, bits and Le; and a codeword's result does not depend on the batch size, its lane or its
+ * wave.
+ * TD_EINVAL, never silently ignored, and a failed call changes nothing: a handle of another precision;
+ * window negative or not a multiple of 16; overlap outside [0, 3 W]; a handle with a td_set_fixed_stop
+ * rule set.  The other way round td_set_fixed_stop with a rule is TD_EINVAL while a window is set (as
+ * td_set_early_stop and td_set_window exclude each other): a windowed fixed decode has no early
+ * termination, and the _stop entry points fill the counts with `iterations`.  td_set_fixed works on
+ * either schedule and the window survives it.  td_reserve sizes everything (the workspace is the exact
+ * schedule's: a sub-block checkpoints only its own 16-step windows); after it a decode allocates and
+ * creates nothing and may be captured into a hipGraph.  A decode is one launch per SISO and iteration
+ * on the decode's stream.  td_profile_read reports the demultiplex and the decode as before;
+ * td_clock_read stays TD_EINVAL; td_rate_dematch's int8 output decodes unchanged.
+ */
+typedef struct td_fixed_window_params {
+    int window;    /* positions per sub-block: 0 = the exact schedule, else a multiple of 16 */
+    int overlap;   /* warm-up positions on each side, 0 .. 3 * window */
+} td_fixed_window_params;
+int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w);
 
 /* Kernel timing (measurement support): while enabled, hipEvents on the decode stream bracket
  * the demultiplex kernel and the turbo kernel of every td_decode_device call.

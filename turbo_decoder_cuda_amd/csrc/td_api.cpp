@@ -129,6 +129,8 @@ struct td_handle {
     td_fixed_params fxp{255, 3};
     // early termination of the fixed-point decoder (td_set_fixed_stop): rule 0 = off; its CRC table is d_crc
     td_stop_params fstop{TD_STOP_NONE, 1, 0};
+    // the fixed-point decoder's sub-block schedule (td_set_fixed_window): window 0 = the exact schedule
+    td_fixed_window_params fwin{0, 0};
 };
 
 namespace td {
@@ -669,7 +671,7 @@ int ensure_fixed_ws(td_handle* h, int B)
 int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le, int32_t* d_iters,
                  hipStream_t st)
 {
-    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop)
+    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop || !td::launch_fixed_window)
         return fail(TD_EHIP, "td_decode_device: this build has no td_fixed.hip");
     int rc = ensure_fixed_ws(h, B);
     if (rc) return rc;
@@ -723,7 +725,10 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         s.used = reinterpret_cast<int32_t*>(ws + c.used);
         e = td::launch_fixed_turbo_stop(a, s, d_bits, d_iters, st);
     } else {
-        e = td::launch_fixed_turbo(a, d_bits, st);
+        if (h->fwin.window)
+            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, d_bits, st);
+        else
+            e = td::launch_fixed_turbo(a, d_bits, st);
         if (e == hipSuccess && d_iters)   // no rule (td_set_fixed_stop): every codeword takes them all
             e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
     }
@@ -1140,6 +1145,9 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
         return TD_OK;
     }
     if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_fixed_stop: unknown rule");
+    if (h->fwin.window)
+        return fail(TD_EINVAL, "td_set_fixed_stop: the TD_FIXED handle has a sub-block schedule (td_set_fixed_window); "
+                               "turn it off first (a windowed fixed decode has no early termination)");
     if (s->min_iters < 1 || s->min_iters > h->p.iterations)
         return fail(TD_EINVAL, "td_set_fixed_stop: min_iters must be in [1, iterations]");
     if (s->rule == TD_STOP_CRC) {
@@ -1187,6 +1195,25 @@ int td_set_fixed(td_handle* h, const td_fixed_params* f)
     if (f->ext_scale_q < 1 || f->ext_scale_q > 4)
         return fail(TD_EINVAL, "td_set_fixed: ext_scale_q must be in [1, 4] (quarters; 4 = no scaling)");
     h->fxp = *f;
+    return TD_OK;
+}
+
+int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed_window: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_window: the handle is not fixed-point (TD_FIXED)");
+    if (!w || w->window == 0) {
+        h->fwin = td_fixed_window_params{0, 0};
+        return TD_OK;
+    }
+    if (w->window < td::fx::kW || w->window % td::fx::kW)
+        return fail(TD_EINVAL, "td_set_fixed_window: the window of a TD_FIXED handle must be 0 or a multiple of 16");
+    if (w->overlap < 0 || w->overlap > 3 * (long long)w->window)
+        return fail(TD_EINVAL, "td_set_fixed_window: the overlap of a TD_FIXED handle must be in [0, 3*window]");
+    if (h->fstop.rule != TD_STOP_NONE)
+        return fail(TD_EINVAL, "td_set_fixed_window: the TD_FIXED handle has an early-termination rule "
+                               "(td_set_fixed_stop); turn it off first");
+    h->fwin = *w;
     return TD_OK;
 }
 

@@ -50,6 +50,10 @@ __attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t
 // without all_iters is its stop row, and d_iters (nullable, [B]) gets s.used
 __attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uint8_t* d_bits,
                                                          int32_t* d_iters, hipStream_t st);
+// the sub-block schedule (td_set_fixed_window): a launch per SISO and iteration on st, grid (Bp / kFxLanes) x
+// sub-blocks, then bitsT -> d_bits as launch_fixed_turbo
+__attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8_t* d_bits,
+                                                     hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

@@ -16,6 +16,9 @@
 //                      lane whose codeword has stopped is skipped, a wave whose lanes have all stopped
 //                      returns, and the transpose back reads row min(row, used - 1) and undoes the interleaved
 //                      order that the stopping decoder keeps its decisions in.
+//   fx_window_siso_kernel  the sub-block schedule (td_set_fixed_window): one SISO of one iteration a launch,
+//                      a wave = 64 codewords x one sub-block (blockIdx.y), the kernel boundary as the
+//                      ordering between a SISO's extrinsic writes and the next SISO's reads.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
 #include <hip/hip_runtime.h>
 
@@ -122,6 +125,16 @@ __global__ __launch_bounds__(kTileThreads) void fx_bits_stop_kernel(const uint8_
     }
 }
 
+// The sub-block schedule: SISO `DEC` of iteration `it`, sub-block blockIdx.y of the wave's 64 codewords.
+// The sub-block index is the block's, so the interleaver entries stay scalar loads and every row access one
+// contiguous piece.  SISO1 reads ext21 and writes ext12, SISO2 the reverse (and bitsT): no launch
+// reads an array that it writes, apart from a sub-block's own checkpoint slots.
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_kernel(fx::FxArgs p, fx::FxWindow w, int it)
+{
+    fx::siso_window_pass<DEC>(p, w, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
+}
+
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
 // addition: no atomics, the same bytes on every run.
 template <bool ACC>
@@ -184,6 +197,21 @@ hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uin
     const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
     hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s.used, p.pinv, p.K, p.B, p.Bp,
                        rows, p.iters, d_bits, d_iters);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8_t* d_bits, hipStream_t st)
+{
+    const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)fx::window_blocks(p.L, w.window));
+    for (int it = 0; it < p.iters; ++it) {
+        hipLaunchKernelGGL(fx_window_siso_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+        hipLaunchKernelGGL(fx_window_siso_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int rows = p.all_iters ? p.iters : 1;
+    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
+    hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
     return hipGetLastError();
 }
 

@@ -262,6 +262,153 @@ TDF_HD void decode_codeword(const FxArgs& p, size_t b)
     }
 }
 
+// The sub-block schedule (td_set_fixed_window), next to FxArgs and not in it, as FxStop is.
+struct FxWindow {
+    int window;           // W: a multiple of kW, so that a sub-block is a run of whole recomputation windows
+    int overlap;          // warm-up steps before a sub-block's start and after its end, any number >= 0
+};
+
+constexpr int window_blocks(int L, int window) { return L / window > 1 ? L / window : 1; }
+
+// One beta step backwards over position i's branch metrics, without an output (the warm-up).
+TDF_HD void beta_step(int (&bt)[8], int S, int P)
+{
+    int c[4];
+    gammas(S, P, c);
+    int n[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) n[s] = imax(c[gsel(s, 0)] + bt[next_state(s, 0)], c[gsel(s, 1)] + bt[next_state(s, 1)]);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) bt[s] = n[s];
+}
+
+// siso_pass for sub-block sb of the sub-block schedule: positions [sb W, (sb + 1) W), the last
+// sub-block up to L.  alpha warms up from max(sb W - overlap, 0) and beta from min(end + overlap, L);
+// a recursion that starts at the trellis' end starts from the terminated state, any other from equal
+// metrics (all 0: never normalised, so the sums stay inside the bounds at the head of this file).  The
+// warm-ups take any start: sixteen steps at a time with their loads ahead of the arithmetic, then the
+// rest one by one.  The sub-block's own steps are siso_pass's: alpha checkpoints at ckpt[w], w the
+// window's index in the whole trellis (sub-blocks own disjoint slots), then per window the recompute,
+// beta, Lambda, f and the stores.  sb must be the same in every lane of a wave.  Sub-blocks of one
+// SISO read ext / xs / xp anywhere and write only their own positions of the other ext array, so
+// they may run in any order or at once; the next SISO may start when all of them are done.
+template <int DEC>
+TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb)
+{
+    const int L = p.L, K = p.K, W = wn.window;
+    const int nS = window_blocks(L, W);
+    const bool live = b < (size_t)p.B;
+    const int start = sb * W, end = sb == nS - 1 ? L : start + W;
+    const bool a_term = start - wn.overlap <= 0, b_term = end + wn.overlap >= L;
+    const int a_from = a_term ? 0 : start - wn.overlap, b_from = b_term ? L : end + wn.overlap;
+    const int w0 = start / kW, w1 = (end + kW - 1) / kW;   // the sub-block's recomputation windows
+
+    {
+        int a[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) a[s] = s && a_term ? kNeg : 0;
+        int i = a_from;
+        for (; i + kW <= start; i += kW) {
+            int S[kW], P[kW];
+#pragma unroll
+            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i + t, S[t], P[t]);
+#pragma unroll
+            for (int t = 0; t < kW; ++t) {
+                int n[8];
+                alpha_step(a, S[t], P[t], n);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) a[s] = n[s];
+            }
+        }
+        for (; i < start; ++i) {
+            int S, P, n[8];
+            load_step<DEC>(p, b, it, i, S, P);
+            alpha_step(a, S, P, n);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) a[s] = n[s];
+        }
+        for (int w = w0; w < w1; ++w) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) p.ckpt[((size_t)w * 8 + s) * p.Bp + b] = a[s];
+            if (w == w1 - 1) break;   // a window that is not the sub-block's last is whole
+            int S[kW], P[kW];
+#pragma unroll
+            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, w * kW + t, S[t], P[t]);
+#pragma unroll
+            for (int t = 0; t < kW; ++t) {
+                int n[8];
+                alpha_step(a, S[t], P[t], n);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) a[s] = n[s];
+            }
+        }
+    }
+
+    int bt[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) bt[s] = s && b_term ? kNeg : 0;
+    {
+        int i = b_from;
+        for (; i - kW >= end; i -= kW) {
+            int S[kW], P[kW];
+#pragma unroll
+            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i - 1 - t, S[t], P[t]);
+#pragma unroll
+            for (int t = 0; t < kW; ++t) beta_step(bt, S[t], P[t]);
+        }
+        for (; i > end; --i) {
+            int S, P;
+            load_step<DEC>(p, b, it, i - 1, S, P);
+            beta_step(bt, S, P);
+        }
+    }
+
+    const int row = p.all_iters ? it : 0;
+    const bool want_bits = DEC == 1 && (p.all_iters || it == p.iters - 1);
+    for (int w = w1 - 1; w >= w0; --w) {
+        const int i0 = w * kW;
+        int S[kW], P[kW];
+#pragma unroll
+        for (int t = 0; t < kW; ++t) {
+            const int i = i0 + t < L ? i0 + t : L - 1;   // past the end (last window): a valid row, never used
+            load_step<DEC>(p, b, it, i, S[t], P[t]);
+        }
+        int A[kW][8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
+#pragma unroll
+        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1]);
+#pragma unroll
+        for (int t = kW - 1; t >= 0; --t) {
+            const int i = i0 + t;
+            if (i < L) {
+                int c[4];
+                gammas(S[t], P[t], c);
+                int e0[8], e1[8];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    e0[s] = c[gsel(s, 0)] + bt[next_state(s, 0)];
+                    e1[s] = c[gsel(s, 1)] + bt[next_state(s, 1)];
+                }
+                int m0 = A[t][0] + e0[0], m1 = A[t][0] + e1[0];
+#pragma unroll
+                for (int s = 1; s < 8; ++s) {
+                    m0 = imax(m0, A[t][s] + e0[s]);
+                    m1 = imax(m1, A[t][s] + e1[s]);
+                }
+                const int llr = (m1 - m0) >> 1;   // Lambda is even
+                const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
+                if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
+                if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
+                if (want_bits && i < K)
+                    p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+#pragma unroll
+                for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
+            }
+        }
+    }
+}
+
 // true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
 TDF_HD bool any_lane(bool run)
 {

@@ -110,6 +110,16 @@ class TurboCodec:
         f = N.TdFixedParams(int(le_max), int(ext_scale_q))
         N.check(N.lib().td_set_fixed(self._h, C.byref(f)))
 
+    def set_fixed_window(self, window: int = 64, overlap: int = 48) -> None:
+        """The fixed-point decoder's sub-block schedule (td_set_fixed_window; precision="fixed" only):
+        sub-blocks of `window` positions (a multiple of 16) that warm up over `overlap` positions on each
+        side and run in parallel, for batches that do not fill the chip with a lane per codeword.
+        window=0: the exact schedule.  Excludes set_fixed_early_stop.  The default overlap is the smallest
+        measured one whose bit and frame errors stay within 1.1x the exact schedule's at 0.4, 0.5 and
+        0.6 dB (K = 6144; DESIGN.md "Fixed point", profiles/fixed/window_ber.json)."""
+        w = N.TdFixedWindowParams(int(window), int(overlap))
+        N.check(N.lib().td_set_fixed_window(self._h, C.byref(w)))
+
     def set_window_maxstar(self, exact: bool) -> None:
         """max* of the windowed log-MAP schedule (td_set_window_maxstar): exact=False the one-read
         table (default), exact=True log_map.cpp's E_algorithm exactly."""
