@@ -7,6 +7,7 @@ import functools
 import numpy as np
 
 import fixed_ref as F
+import fixed_size_cases
 import llr_families
 import pyoracle as O
 import window_stop_cases as W
@@ -18,6 +19,8 @@ STEPS = 8   # steps per unit LLR of the GPU cases
 QPP = {8: (3, 4), 13: (1, 0), 16: (1, 4), 29: (1, 0), 40: (3, 10), 200: (13, 50), 1024: (31, 64), 6144: (263, 480)}
 _z = np.load(f"{GOLD}/frames_K10000_e0.8_s43.npz")
 QPP[int(_z["K"])] = (int(_z["f1"]), int(_z["f2"]))
+for _K in fixed_size_cases.SIZES:   # every residue of L mod 16, non-identity interleavers
+    QPP.setdefault(_K, fixed_size_cases.interleaver(_K))
 
 
 def _frozen(*arrays):

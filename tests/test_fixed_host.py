@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import fixed_ref as F
+import fixed_size_cases as Z
 import pyoracle as O
 from turbo_decoder_cuda_amd import _native as N
 
@@ -120,10 +121,13 @@ def _run_core(exe, tmp_path, q, K, f1, f2, iters, all_iters, le_max, scale):
 
 @pytest.mark.parametrize("K,f1,f2,iters,setting", [(8, 3, 4, 3, (255, 4)), (13, 1, 0, 2, (31, 2)), (16, 1, 4, 2, (255, 3)),
                                                    (29, 1, 0, 2, (127, 3)), (40, 3, 10, 4, (255, 3)),
-                                                   (1024, 31, 64, 3, (127, 3))])
+                                                   (1024, 31, 64, 3, (127, 3))]
+                         + [(K, *Z.interleaver(K), 3, Z.setting(K)) for K in Z.SIZES])
 def test_kernel_arithmetic_on_the_host_equals_restatement(core_host, tmp_path, K, f1, f2, iters, setting):
-    """Block lengths round the 16-step window (L = 11, 16, 19, 32, 43, 1027), AWGN at 16 steps per
-    unit next to the saturated patterns, every row and every Le; ASan watches the workspace's bounds."""
+    """Block lengths round the 16-step window (L = 11, 16, 19, 32, 43, 1027) and fixed_size_cases.SIZES
+    (every residue of L mod 16 with one, two and eight windows; non-identity interleavers), AWGN at 16
+    steps per unit next to the saturated patterns, every row and every Le; ASan watches the workspace's
+    bounds."""
     n = 3 * K + 12
     q = np.concatenate([
         F.quantise(O.synth_batch(K, f1, f2, 1.0, 5, 3)[1], 16),

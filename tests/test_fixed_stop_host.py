@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fixed_size_cases as Z
 import fixed_stop_cases as S
 import pyoracle as O
 import window_stop_cases as W
@@ -61,7 +62,8 @@ def _run_core(exe, tmp_path, q, K, iters, all_iters, setting, rule, min_iters, p
 
 # block lengths round the 16-step window (L = 11, 16, 19, 32, 43, 1027), as test_fixed_host.py
 @pytest.mark.parametrize("K,iters,setting", [(8, 4, (255, 4)), (13, 4, (31, 2)), (16, 4, (255, 3)), (29, 4, (127, 3)),
-                                             (40, 6, (255, 3)), (1024, 5, (127, 3))])
+                                             (40, 6, (255, 3)), (1024, 5, (127, 3))]
+                         + [(K, 4, Z.setting(K)) for K in Z.SIZES if K not in (8, 13, 16)])
 def test_stopping_lane_code_on_the_host_equals_rule_on_restatement(core_host, tmp_path, K, iters, setting):
     """HDA, and CRC with gCRC24B where K > 24; min_iters 1 and 3; with and without all_iters: the rows
     (frozen), the counts, the Le of iterations <= used -- and nothing written after a stop."""

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import fixed_ref as F
+import fixed_size_cases as Z
 import fixed_window_ref as FW
 import pyoracle as O
 from turbo_decoder_cuda_amd import _native as N
@@ -108,6 +109,8 @@ CASES = [(8, 3, 4, 3, (255, 4), 16, 0), (8, 3, 4, 3, (255, 4), 16, 48),
          (40, 3, 10, 4, (255, 3), 16, 0), (40, 3, 10, 4, (255, 3), 16, 5), (40, 3, 10, 4, (255, 3), 16, 16),
          (40, 3, 10, 4, (255, 3), 16, 48),
          (1024, 31, 64, 3, (127, 3), 32, 7), (1024, 31, 64, 3, (255, 3), 64, 32), (1024, 31, 64, 3, (255, 3), 128, 384)]
+# every residue of L mod 16 and the longest last sub-block (fixed_size_cases.SIZES), non-identity interleavers
+CASES += [(K, *Z.interleaver(K), 3, Z.setting(K), W, g) for K in Z.SIZES for W, g in Z.WINDOWS]
 
 
 @pytest.mark.parametrize("K,f1,f2,iters,setting,W,g", CASES)

@@ -218,6 +218,7 @@ hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8
 hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out, int accumulate, hipStream_t st)
 {
     const int nout = 3 * p.K + 12;
+    // 512: crossed by tests/test_gpu_ratematch_batches.py test_rate_dematch_int8_past_the_grid_cap (B = 513, 1100, 1537)
     const dim3 grid((unsigned)((nout + kTileThreads - 1) / kTileThreads), (unsigned)(p.B < 512 ? p.B : 512));
     if (accumulate)
         hipLaunchKernelGGL(fx_dematch_kernel<true>, grid, dim3(kTileThreads), 0, st, p, d_e, d_out);

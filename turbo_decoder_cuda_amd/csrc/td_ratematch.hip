@@ -114,11 +114,13 @@ __global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, co
 }
 
 constexpr int kRmRows = 16;
+// crossed by tests/test_gpu_ratematch_batches.py test_rate_dematch_past_the_grid_cap (B = 513, 1100, 1537)
 constexpr unsigned kRmGridY = 512;   // codewords beyond it share a workgroup (and its table reads)
 
 template <typename T>
 hipError_t launch_match_t(const RmParams& p, const void* in, void* e, hipStream_t st)
 {
+    // 65535: crossed by tests/test_gpu_ratematch_batches.py test_rate_match_past_the_grid_cap (B = 65600)
     const dim3 grid((unsigned)(((size_t)p.E + kRmThreads - 1) / kRmThreads), (unsigned)(p.B < 65535 ? p.B : 65535));
     hipLaunchKernelGGL(rate_match_kernel<T>, grid, dim3(kRmThreads), 0, st, p, static_cast<const T*>(in),
                        static_cast<T*>(e));
