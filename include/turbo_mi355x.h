@@ -247,8 +247,8 @@ int td_crc24_syndromes(int K, uint32_t poly, uint32_t* table /* [K] */);
  * td_rate_dematch takes int8 d_e and int8 d_llr (see there); td_rate_match with elem_size 1 moves int8.
  * TD_EINVAL on a TD_FIXED handle, never silently ignored: td_set_window, td_set_window_maxstar,
  * td_set_early_stop, td_set_window_stop, td_siso_host, td_clock_read, td_debug_set_stamps.  The other
- * way round, td_set_fixed, td_set_fixed_stop and td_set_fixed_window are TD_EINVAL on a handle of another
- * precision.
+ * way round, td_set_fixed, td_set_fixed_stop, td_set_fixed_window and td_set_fixed_window_stop are TD_EINVAL
+ * on a handle of another precision.
  *
  * td_set_fixed: le_max in [1, 255], ext_scale_q in [1, 4] (quarters; 4 = no scaling); the default is
  * {255, 3}, which NULL restores.  TD_EINVAL on a handle of another precision or a value out of range; a
@@ -315,12 +315,14 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s);
  * TD_EINVAL, never silently ignored, and a failed call changes nothing: a handle of another precision;
  * window negative or not a multiple of 16; overlap outside [0, 3 W]; a handle with a td_set_fixed_stop
  * rule set.  The other way round td_set_fixed_stop with a rule is TD_EINVAL while a window is set (as
- * td_set_early_stop and td_set_window exclude each other): a windowed fixed decode has no early
- * termination, and the _stop entry points fill the counts with `iterations`.  td_set_fixed works on
- * either schedule and the window survives it.  td_reserve sizes everything (the workspace is the exact
- * schedule's: a sub-block checkpoints only its own 16-step windows); after it a decode allocates and
- * creates nothing and may be captured into a hipGraph.  A decode is one launch per SISO and iteration
- * on the decode's stream.  td_profile_read reports the demultiplex and the decode as before;
+ * td_set_early_stop and td_set_window exclude each other): the windowed fixed decode's early
+ * termination is td_set_fixed_window_stop's (below), and without it the _stop entry points fill the counts
+ * with `iterations`.  td_set_fixed works on either schedule and the window survives it.  td_reserve sizes
+ * everything (the workspace is the exact schedule's -- a sub-block checkpoints only its own 16-step
+ * windows -- and 6 bytes per 16 positions and codeword for td_set_fixed_window_stop's evidence, carved
+ * whether or not a rule is set: 2.2 % more at K = 6144); after it a decode allocates and creates nothing
+ * and may be captured into a hipGraph.  Without a rule a decode is one launch per SISO and iteration on
+ * the decode's stream.  td_profile_read reports the demultiplex and the decode as before;
  * td_clock_read stays TD_EINVAL; td_rate_dematch's int8 output decodes unchanged.
  */
 typedef struct td_fixed_window_params {
@@ -328,6 +330,42 @@ typedef struct td_fixed_window_params {
     int overlap;   /* warm-up positions on each side, 0 .. 3 * window */
 } td_fixed_window_params;
 int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w);
+/*
+ * Per-codeword early termination of the fixed-point decoder's sub-block schedule: the fourth sibling of
+ * td_set_early_stop, td_set_window_stop and td_set_fixed_stop, with their two rules, td_stop_params,
+ * frozen-row convention and iters_used output, judged on the windowed fixed decode's own rows.  Off by
+ * default; with it off a windowed fixed decode launches the kernels it always did and the _stop entry
+ * points fill the counts with `iterations`.
+ *   row(n)  the hard-decision row after n iterations of the full td_set_fixed_window decode with the
+ *           handle's window, overlap and td_set_fixed setting (row n-1 of an all_iters decode with the
+ *           rule off).
+ *   TD_STOP_HDA  codeword b stops after the smallest n >= max(2, min_iters) with row(n) == row(n-1) on
+ *                all K bits; without such an n, at `iterations`.
+ *   TD_STOP_CRC  after the smallest n >= max(1, min_iters) with CRC-24(row(n)) == 0 (td_crc24_host's
+ *                convention).  Needs K > 24.
+ * iters_used[b] = n and the decoded bits of b are row(n).  With all_iters, rows <= n equal the full
+ * decode's and rows n+1 .. iterations are copies of row(n).  d_le entries of iterations <= n equal the
+ * full decode's; later entries are unspecified (the decoder does not write them).  min_iters ==
+ * iterations reproduces the rule-off decode byte for byte, every count `iterations`.  A codeword's
+ * result does not depend on its lane, its wave of 64, its batch or the batch size.
+ * Valid only on a TD_FIXED handle whose schedule is the sub-block one (td_set_fixed_window with window > 0
+ * first): otherwise TD_EINVAL, NULL included.  Argument checks as td_set_fixed_stop (TD_EINVAL: unknown
+ * rule, min_iters outside [1, iterations], TD_STOP_CRC with crc_poly == 0, with coefficients above the
+ * 24 low-order ones or with K <= 24); a failed call changes nothing.  NULL or rule TD_STOP_NONE turns the
+ * rule off.  The rule survives td_set_fixed and a later td_set_fixed_window with window > 0;
+ * td_set_fixed_window(NULL or window 0) clears it, as td_set_window does td_set_window_stop's.
+ * td_set_fixed_stop stays TD_EINVAL while a window is set, and td_set_fixed_window while a
+ * td_set_fixed_stop rule is.
+ * A decode with the rule resets the per-codeword state on its stream, then launches per iteration
+ * SISO1, SISO2 and a decision kernel (one thread per codeword): a wave all of whose 64 codewords have
+ * stopped returns at once, which is where time is saved; a stopped codeword in a running wave is
+ * skipped.  The state and the evidence live in the workspace that td_reserve sizes, and the CRC rule's
+ * device table is built here, so after td_reserve a decode allocates and creates nothing and may be
+ * captured into a hipGraph (a replay repeats the reset).  td_decode_device_stop / td_decode_host_stop
+ * fill the counts; the plain entry points behave like them with a null count pointer.  td_clock_read
+ * stays TD_EINVAL.
+ */
+int td_set_fixed_window_stop(td_handle* h, const td_stop_params* s);
 
 /* Kernel timing (measurement support): while enabled, hipEvents on the decode stream bracket
  * the demultiplex kernel and the turbo kernel of every td_decode_device call.

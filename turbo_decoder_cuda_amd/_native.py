@@ -30,7 +30,7 @@ EXPORTS = (
     "td_debug_workspace_bytes", "td_set_window_maxstar", "td_set_early_stop", "td_decode_device_stop",
     "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
     "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
-    "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window",
+    "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window", "td_set_fixed_window_stop",
 )
 
 
@@ -133,6 +133,8 @@ def lib() -> C.CDLL:
         L.td_set_fixed_stop.argtypes = [P, C.POINTER(TdStopParams)]
     if hasattr(L, "td_set_fixed_window"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_set_fixed_window.argtypes = [P, C.POINTER(TdFixedWindowParams)]
+    if hasattr(L, "td_set_fixed_window_stop"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_set_fixed_window_stop.argtypes = [P, C.POINTER(TdStopParams)]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

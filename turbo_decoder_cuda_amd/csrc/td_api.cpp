@@ -131,6 +131,9 @@ struct td_handle {
     td_stop_params fstop{TD_STOP_NONE, 1, 0};
     // the fixed-point decoder's sub-block schedule (td_set_fixed_window): window 0 = the exact schedule
     td_fixed_window_params fwin{0, 0};
+    // early termination of the sub-block schedule (td_set_fixed_window_stop): rule 0 = off; its CRC table is d_crc
+    // (a fixed handle has a rule of one kind at most: td_set_fixed_stop's needs window 0, this one a window)
+    td_stop_params fwstop{TD_STOP_NONE, 1, 0};
 };
 
 namespace td {
@@ -671,7 +674,8 @@ int ensure_fixed_ws(td_handle* h, int B)
 int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le, int32_t* d_iters,
                  hipStream_t st)
 {
-    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop || !td::launch_fixed_window)
+    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop || !td::launch_fixed_window ||
+        !td::launch_fixed_window_stop)
         return fail(TD_EHIP, "td_decode_device: this build has no td_fixed.hip");
     int rc = ensure_fixed_ws(h, B);
     if (rc) return rc;
@@ -724,6 +728,16 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
         s.used = reinterpret_cast<int32_t*>(ws + c.used);
         e = td::launch_fixed_turbo_stop(a, s, d_bits, d_iters, st);
+    } else if (h->fwin.window && h->fwstop.rule != TD_STOP_NONE) {
+        const bool hda = h->fwstop.rule == TD_STOP_HDA;
+        td::fx::FxStop s{};
+        s.rule = h->fwstop.rule;
+        s.first = std::max(hda ? 2 : 1, h->fwstop.min_iters);
+        s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
+        s.used = reinterpret_cast<int32_t*>(ws + c.used);
+        e = td::launch_fixed_window_stop(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, s,
+                                         reinterpret_cast<uint32_t*>(ws + c.ev),
+                                         reinterpret_cast<uint16_t*>(ws + c.hist), d_bits, d_iters, st);
     } else {
         if (h->fwin.window)
             e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, d_bits, st);
@@ -1147,7 +1161,7 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
     if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_fixed_stop: unknown rule");
     if (h->fwin.window)
         return fail(TD_EINVAL, "td_set_fixed_stop: the TD_FIXED handle has a sub-block schedule (td_set_fixed_window); "
-                               "turn it off first (a windowed fixed decode has no early termination)");
+                               "its rule is set by td_set_fixed_window_stop");
     if (s->min_iters < 1 || s->min_iters > h->p.iterations)
         return fail(TD_EINVAL, "td_set_fixed_stop: min_iters must be in [1, iterations]");
     if (s->rule == TD_STOP_CRC) {
@@ -1167,6 +1181,41 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
         TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     h->fstop = *s;
+    return TD_OK;
+}
+
+int td_set_fixed_window_stop(td_handle* h, const td_stop_params* s)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed_window_stop: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_window_stop: the handle is not fixed-point (TD_FIXED)");
+    if (!h->fwin.window)
+        return fail(TD_EINVAL, "td_set_fixed_window_stop: the TD_FIXED handle's schedule is not the sub-block one "
+                               "(td_set_fixed_window first; the exact schedule's rule is td_set_fixed_stop)");
+    if (!s || s->rule == TD_STOP_NONE) {
+        h->fwstop = td_stop_params{TD_STOP_NONE, 1, 0};
+        return TD_OK;
+    }
+    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC)
+        return fail(TD_EINVAL, "td_set_fixed_window_stop: unknown rule");
+    if (s->min_iters < 1 || s->min_iters > h->p.iterations)
+        return fail(TD_EINVAL, "td_set_fixed_window_stop: min_iters must be in [1, iterations]");
+    if (s->rule == TD_STOP_CRC) {
+        if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
+            return fail(TD_EINVAL, "td_set_fixed_window_stop: crc_poly must be the 24 low-order coefficients, non-zero");
+        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_fixed_window_stop: TD_STOP_CRC needs K > 24");
+        TD_HIP(hipSetDevice(h->p.device));
+        // the table lives on the device from here on: a decode allocates nothing for the rule
+        if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
+            h->d_crc = nullptr;
+            return fail(TD_ENOMEM, "td_set_fixed_window_stop: hipMalloc failed");
+        }
+        std::vector<uint32_t> syn((size_t)h->p.K), tab((size_t)h->p.K);
+        td::crc24_syndromes(h->p.K, s->crc_poly, syn.data());
+        for (int i = 0; i < h->p.K; ++i) tab[i] = syn[h->pi[i]];   // in the order SISO2 meets the bits (FxStop)
+        TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
+        TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    h->fwstop = *s;
     return TD_OK;
 }
 
@@ -1204,6 +1253,7 @@ int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w)
     if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_window: the handle is not fixed-point (TD_FIXED)");
     if (!w || w->window == 0) {
         h->fwin = td_fixed_window_params{0, 0};
+        h->fwstop = td_stop_params{TD_STOP_NONE, 1, 0};   // the sub-block schedule's rule goes with it
         return TD_OK;
     }
     if (w->window < td::fx::kW || w->window % td::fx::kW)

@@ -17,7 +17,7 @@ namespace td {
 constexpr int kFxLanes = 64;   // codewords of a wave = of a workgroup
 
 struct FxCarve {
-    size_t xs, xp1, xp2, ext12, ext21, ckpt, bitsT, used, total;
+    size_t xs, xp1, xp2, ext12, ext21, ckpt, bitsT, used, ev, hist, total;
     size_t Bp;
 };
 
@@ -36,7 +36,14 @@ inline FxCarve fx_carve(int B, int K, int iters)
     c.ckpt = c.ext21 + up((size_t)K * Bp * 2);
     c.bitsT = c.ckpt + up(nW * 8 * Bp * 4);
     c.used = c.bitsT + up((size_t)iters * K * Bp);   // a row per iteration (all_iters, early termination)
-    c.total = c.used + up(Bp * 4);                   // int32 [Bp]: iterations used (td_set_fixed_stop), always carved
+    c.ev = c.used + up(Bp * 4);                      // int32 [Bp]: iterations used (td_set_fixed_stop), always carved
+    // uint32 [nW][Bp]: a word of evidence per sub-block and codeword (td_set_fixed_window_stop); nW bounds the
+    // sub-blocks of every allowed window (>= kW).  Then uint16 [nW][Bp]: the rule's HDA form keeps the sixteen
+    // decisions of every 16-step window packed for the next iteration's comparison.  Both are always carved, so
+    // that td_reserve does not depend on the rule: 6 B per 16 positions and codeword, 2.2 % of the workspace at
+    // K = 6144 and 8 iterations.
+    c.hist = c.ev + up(nW * Bp * 4);
+    c.total = c.hist + up(nW * Bp * 2);
     return c;
 }
 
@@ -54,6 +61,12 @@ __attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, co
 // sub-blocks, then bitsT -> d_bits as launch_fixed_turbo
 __attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8_t* d_bits,
                                                      hipStream_t st);
+// the sub-block schedule with early termination (td_set_fixed_window_stop): s.used is reset on st, then per
+// iteration SISO1, SISO2 and the judge, then the frozen rows and d_iters as launch_fixed_turbo_stop; d_ev and
+// d_hist are the carve's ev and hist
+__attribute__((weak)) hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s,
+                                                          uint32_t* d_ev, uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters,
+                                                          hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

@@ -19,6 +19,12 @@
 //   fx_window_siso_kernel  the sub-block schedule (td_set_fixed_window): one SISO of one iteration a launch,
 //                      a wave = 64 codewords x one sub-block (blockIdx.y), the kernel boundary as the
 //                      ordering between a SISO's extrinsic writes and the next SISO's reads.
+//   fx_window_siso_stop_kernel, fx_window_judge_kernel  the sub-block schedule with early termination
+//                      (td_set_fixed_window_stop): used[b] is the state (0 = running), a wave with no running
+//                      codeword returns, SISO2 leaves each sub-block's evidence in the workspace (and, for
+//                      the next iteration's HDA comparison, every 16-step window's decisions packed) and the
+//                      judge, a launch of its own after SISO2's, folds it and stops the codeword; then
+//                      fx_bits_stop_kernel.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
 #include <hip/hip_runtime.h>
 
@@ -135,6 +141,25 @@ __global__ __launch_bounds__(kFxLanes) void fx_window_siso_kernel(fx::FxArgs p, 
     fx::siso_window_pass<DEC>(p, w, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
 }
 
+// The same with early termination (td_set_fixed_window_stop), on the same grid: a wave whose 64 codewords
+// have all stopped returns at once, and SISO2 leaves the sub-block's evidence at ev[blockIdx.y][b].
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
+                                                                        uint32_t* __restrict__ ev,
+                                                                        uint16_t* __restrict__ hist, int it)
+{
+    fx::siso_window_stop<DEC>(p, w, s, ev, hist, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
+}
+
+// One thread per codeword after SISO2's launch of iteration `it`: folds the sub-blocks' evidence and
+// sets used[b] where the codeword stops.  The kernel boundaries order it after the stores of ev and
+// before the next launch's reads of used.
+__global__ __launch_bounds__(kTileThreads) void fx_window_judge_kernel(fx::FxArgs p, fx::FxStop s,
+                                                                       const uint32_t* __restrict__ ev, int nS, int it)
+{
+    fx::window_judge(p, s, ev, nS, (size_t)blockIdx.x * kTileThreads + threadIdx.x, it);
+}
+
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
 // addition: no atomics, the same bytes on every run.
 template <bool ACC>
@@ -212,6 +237,28 @@ hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8
     const int rows = p.all_iters ? p.iters : 1;
     const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
     hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s, uint32_t* d_ev,
+                                    uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(s.used, 0, p.Bp * sizeof(int32_t), st);   // every codeword runs
+    if (e != hipSuccess) return e;
+    const int nS = fx::window_blocks(p.L, w.window);
+    const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)nS);
+    const dim3 jgrid((unsigned)((p.Bp + kTileThreads - 1) / kTileThreads));
+    for (int it = 0; it < p.iters; ++it) {
+        hipLaunchKernelGGL(fx_window_siso_stop_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
+        hipLaunchKernelGGL(fx_window_siso_stop_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
+        hipLaunchKernelGGL(fx_window_judge_kernel, jgrid, dim3(kTileThreads), 0, st, p, s, d_ev, nS, it);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int rows = p.all_iters ? p.iters : 1;
+    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
+    hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s.used, p.pinv, p.K, p.B, p.Bp,
+                       rows, p.iters, d_bits, d_iters);
     return hipGetLastError();
 }
 

@@ -54,14 +54,14 @@ struct FxArgs {
     size_t Bp;            // codewords of the padded batch (the row pitch)
 };
 
-// Early termination (td_set_fixed_stop), next to FxArgs and not in it: tests/fixed_core_host.cpp
-// initialises FxArgs member by member.
+// Early termination (td_set_fixed_stop, and td_set_fixed_window_stop on the sub-block schedule), next to
+// FxArgs and not in it: tests/fixed_core_host.cpp initialises FxArgs member by member.
 struct FxStop {
     int rule;             // 1: the rows repeat (HDA), 2: the row's CRC-24 is zero (enum td_stop_rule)
     int first;            // the smallest iteration count a codeword may stop after: max(HDA ? 2 : 1, min_iters)
     const int* syn;       // [K] CRC, by interleaved position i: the remainder of the row with only bit pi(i) set
                           //     (td_crc.h's syndrome[pi[i]]), as bit patterns
-    int32_t* used;        // [Bp] the iterations each codeword took
+    int32_t* used;        // [Bp] the iterations each codeword took (the sub-block schedule: 0 while it runs)
 };
 
 // f of the contract: towards zero, symmetric in sign, clamped
@@ -292,8 +292,21 @@ TDF_HD void beta_step(int (&bt)[8], int S, int P)
 // beta, Lambda, f and the stores.  sb must be the same in every lane of a wave.  Sub-blocks of one
 // SISO read ext / xs / xp anywhere and write only their own positions of the other ext array, so
 // they may run in any order or at once; the next SISO may start when all of them are done.
-template <int DEC>
-TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb)
+//
+// STOP (td_set_fixed_window_stop, sp its rule): the caller runs only the lanes whose codeword has not
+// stopped.  SISO2 writes row `it` of bitsT in every iteration, by interleaved position as siso_pass<1, true>
+// does, and in a judged iteration (it + 1 >= sp->first) stores the rule's evidence on the sub-block's
+// own positions below K at ev[sb][b]: HDA the bits that differ from row it - 1 (OR over the windows),
+// CRC the XOR of syn[i] over the 1 bits.  HDA's previous bits are not read back from bitsT: sixteen
+// byte loads a window cost this schedule, which keeps the chip full, 16-20 % of the decode where nothing
+// converges.  A lane leaves the sixteen bits of each of its 16-step windows packed at hist[w][b] (w the
+// window's index in the whole trellis, as for ckpt) when the next iteration is judged, and the window's
+// previous bits are one 16-bit load together with the window's inputs; the slot is the lane's own, read
+// before it is written.  The codeword's evidence is the fold of its sub-blocks' words, which the launch
+// after SISO2's makes (fx_window_judge_kernel): no atomics, and no launch reads a word of ev that it writes.
+template <int DEC, bool STOP>
+TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop* sp, uint32_t* ev, uint16_t* hist,
+                               size_t b, int it, int sb)
 {
     const int L = p.L, K = p.K, W = wn.window;
     const int nS = window_blocks(L, W);
@@ -363,8 +376,11 @@ TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int 
         }
     }
 
-    const int row = p.all_iters ? it : 0;
-    const bool want_bits = DEC == 1 && (p.all_iters || it == p.iters - 1);
+    const int row = STOP || p.all_iters ? it : 0;
+    const bool want_bits = DEC == 1 && (STOP || p.all_iters || it == p.iters - 1);
+    const bool judge = STOP && DEC == 1 && it + 1 >= sp->first;
+    const bool hda = STOP && DEC == 1 && sp->rule == 1;
+    int acc = 0;
     for (int w = w1 - 1; w >= w0; --w) {
         const int i0 = w * kW;
         int S[kW], P[kW];
@@ -373,6 +389,8 @@ TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int 
             const int i = i0 + t < L ? i0 + t : L - 1;   // past the end (last window): a valid row, never used
             load_step<DEC>(p, b, it, i, S[t], P[t]);
         }
+        unsigned was = 0, now = 0;   // HDA: bit t = the bit of position i0 + t in row it - 1, in row it
+        if (STOP && judge && hda) was = hist[(size_t)w * p.Bp + b];   // first >= 2: the window's word of row it - 1
         int A[kW][8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
@@ -400,13 +418,34 @@ TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int 
                 const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
                 if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
                 if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
-                if (want_bits && i < K)
-                    p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+                if (!STOP) {
+                    if (want_bits && i < K)
+                        p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
+                } else if (want_bits && i < K) {
+                    const int bit = llr < 0 ? 0 : 1;
+                    p.bitsT[((size_t)row * K + (size_t)i) * p.Bp + b] = (uint8_t)bit;
+                    if (hda)
+                        now |= (unsigned)bit << t;
+                    else if (judge)
+                        acc ^= -bit & table_entry(sp->syn, i);
+                }
 #pragma unroll
                 for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
             }
         }
+        if (STOP && hda) {
+            if (judge) acc |= (int)(was ^ now);
+            if (it + 2 >= sp->first && it + 1 < p.iters)   // there is a next iteration, and it is judged
+                hist[(size_t)w * p.Bp + b] = (uint16_t)now;
+        }
     }
+    if (STOP && judge) ev[(size_t)sb * p.Bp + b] = (uint32_t)acc;
+}
+
+template <int DEC>
+TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb)
+{
+    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, b, it, sb);
 }
 
 // true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
@@ -441,6 +480,48 @@ TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b)
         if (!any_lane(run)) break;
     }
     s.used[b] = used;
+}
+
+// One lane of the stopping sub-block kernels: SISO `DEC` of iteration `it`, sub-block sb of codeword b.
+// s.used is the state that the decode resets to 0 at its start: 0 = running, n = stopped after n
+// iterations.  A wave none of whose lanes runs returns on the ballot -- where the time is saved -- and a
+// stopped lane of a running wave is skipped by a branch and writes nothing; a lane of the padding never
+// runs.  sb must be the same in every lane of a wave.
+template <int DEC>
+TDF_HD void siso_window_stop(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist, size_t b,
+                             int it, int sb)
+{
+    const bool run = b < (size_t)p.B && s.used[b] == 0;
+    if (!any_lane(run)) return;
+    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, b, it, sb);
+}
+
+// The decision after SISO2's launch of iteration `it`, one call per codeword: a running codeword stops
+// after n = it + 1 iterations if n >= s.first and the fold of its nS sub-blocks' evidence (OR for HDA,
+// XOR for CRC) is zero, and at n = p.iters in any case.
+TDF_HD void window_judge(const FxArgs& p, const FxStop& s, const uint32_t* ev, int nS, size_t b, int it)
+{
+    if (b >= (size_t)p.B || s.used[b] != 0) return;
+    const int n = it + 1;
+    bool stop = n == p.iters;
+    if (!stop && n >= s.first) {
+        const bool hda = s.rule == 1;
+        uint32_t acc = 0;
+        int sb = 0;
+        for (; sb + 8 <= nS; sb += 8) {   // eight loads in flight: one thread's fold is a chain of load latencies
+            uint32_t v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = ev[(size_t)(sb + j) * p.Bp + b];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc = hda ? acc | v[j] : acc ^ v[j];
+        }
+        for (; sb < nS; ++sb) {
+            const uint32_t v = ev[(size_t)sb * p.Bp + b];
+            acc = hda ? acc | v : acc ^ v;
+        }
+        stop = acc == 0;
+    }
+    if (stop) s.used[b] = n;
 }
 
 }  // namespace fx

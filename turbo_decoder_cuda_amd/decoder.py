@@ -114,11 +114,14 @@ class TurboCodec:
         """The fixed-point decoder's sub-block schedule (td_set_fixed_window; precision="fixed" only):
         sub-blocks of `window` positions (a multiple of 16) that warm up over `overlap` positions on each
         side and run in parallel, for batches that do not fill the chip with a lane per codeword.
-        window=0: the exact schedule.  Excludes set_fixed_early_stop.  The default overlap is the smallest
+        window=0: the exact schedule.  Excludes set_fixed_early_stop (its rule is
+        set_fixed_window_early_stop's).  The default overlap is the smallest
         measured one whose bit and frame errors stay within 1.1x the exact schedule's at 0.4, 0.5 and
         0.6 dB (K = 6144; DESIGN.md "Fixed point", profiles/fixed/window_ber.json)."""
         w = N.TdFixedWindowParams(int(window), int(overlap))
         N.check(N.lib().td_set_fixed_window(self._h, C.byref(w)))
+        if not int(window) and self._window_stop:   # td_set_fixed_window(0) clears the sub-block schedule's rule
+            self.early_stop, self._window_stop = None, False
 
     def set_window_maxstar(self, exact: bool) -> None:
         """max* of the windowed log-MAP schedule (td_set_window_maxstar): exact=False the one-read
@@ -167,7 +170,20 @@ class TurboCodec:
             raise ValueError(f"rule must be 'hda', 'crc' or None, got {rule!r}")
         s = N.TdStopParams(_STOP_RULES[rule], int(min_iters), int(crc_poly) & 0xFFFFFFFF)
         N.check(N.lib().td_set_fixed_stop(self._h, C.byref(s)))
+        if not self._window_stop:   # (with a window set only None gets here, and leaves the window's rule alone)
+            self.early_stop = rule
+
+    def set_fixed_window_early_stop(self, rule=None, min_iters: int = 1, crc_poly: int = N.CRC24B) -> None:
+        """Per-codeword early termination of the fixed-point decoder's sub-block schedule
+        (td_set_fixed_window_stop; after set_fixed_window): the rules, arguments and frozen-row convention of
+        set_early_stop, judged on the windowed fixed decode's own rows.  The rule survives set_fixed and
+        later set_fixed_window calls with a window; set_fixed_window(0) clears it."""
+        if rule not in _STOP_RULES:
+            raise ValueError(f"rule must be 'hda', 'crc' or None, got {rule!r}")
+        s = N.TdStopParams(_STOP_RULES[rule], int(min_iters), int(crc_poly) & 0xFFFFFFFF)
+        N.check(N.lib().td_set_fixed_window_stop(self._h, C.byref(s)))
         self.early_stop = rule
+        self._window_stop = rule is not None
 
     def debug_window_layout(self, run: int = 0, run_a: int = 0, parts: int = 0) -> None:
         """Windowed kernels' layout for tests and measurements (td_debug_window_layout): sub-blocks
