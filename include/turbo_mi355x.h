@@ -260,6 +260,47 @@ typedef struct td_fixed_params {
 } td_fixed_params;
 int td_set_fixed(td_handle* h, const td_fixed_params* f);
 /*
+ * Integer log-MAP on a TD_FIXED handle: max plus a small correction table (max*), the fixed decoder's form
+ * of the float decoders' TD_ALGO_LOGMAP.  Off by default (Max-Log-MAP, whose kernels do not change; td_create
+ * keeps taking TD_ALGO_MAXLOG only for TD_FIXED); NULL turns it off.  With a table set every max(a, b) of the
+ * TD_FIXED contract above -- and of td_set_fixed_window's sub-blocks, warm-ups included -- becomes
+ *   maxs(a, b) = max(a, b) + corr[min(|a - b| >> shift, 7)]
+ * maxs rounds, so it is not associative, and the order of every operation is part of the contract:
+ *   alpha   into state j: maxs(alpha[p0] + gamma, alpha[p1] + gamma), p0 the u = 0 predecessor of j first.
+ *   beta    of state s: maxs(gamma_0(s) + beta[next(s,0)], gamma_1(s) + beta[next(s,1)]).
+ *   Lambda  each of its two terms is a left fold with maxs over the source state s = 0, 1, ..., 7 of
+ *           alpha[s] + gamma_u(s) + beta[next(s,u)]; Lambda = the u = 1 fold minus the u = 0 fold.
+ * Lambda is no longer even: LLR = Lambda / 2 truncated towards zero, as f truncates (on even Lambda the
+ * contract's >> 1).  The hard bit, f, the iteration, the sub-block geometry, both early-termination rules
+ * (judged on the rows of the decode with the table) and the layouts of d_bits and d_le are unchanged.
+ * corr[7] == 0 makes maxs of a reachable sum and an unreachable one the reachable sum exactly, so no output
+ * depends on the value that stands for "unreachable".  With entries <= 63 a step adds at most 509 + 63 to a
+ * state metric, |alpha|, |beta| <= 572 * 10003 < 2^23 and a Lambda term with its fold's corrections stays below
+ * 2^24: nothing saturates but the contract's two clamps, and every value is defined bit for bit
+ * (tests/fixed_maxstar_ref.py restates it).  An all-zero table is Max-Log-MAP.
+ * td_set_fixed's default {255, 3} is not changed by a table, but its 3/4 scale exists to compensate Max-Log-MAP's
+ * overestimate: log-MAP wants {255, 4} (DESIGN.md "Fixed point").
+ * The table applies to all four fixed schedules -- exact, td_set_fixed_stop, td_set_fixed_window,
+ * td_set_fixed_window_stop -- whatever the order of the calls, and survives td_set_fixed, the window setters and
+ * the stop setters.  It travels as kernel arguments: the workspace does not grow, and after td_reserve a decode
+ * allocates nothing and may be captured into a hipGraph.
+ * TD_EINVAL, never silently ignored, and a failed call changes nothing: a null handle or one of another
+ * precision; shift outside [0, 8]; an entry above 63; corr[7] != 0.
+ *
+ * td_fixed_maxstar_table (host only, no handle): the table for inputs quantised at steps_per_unit steps per
+ * unit LLR.  The integer branch metric is twice the float one, so a nat is s = 2 steps_per_unit metric steps:
+ *   corr[j] = floor(s log1p(exp(-(j + 1/2) 2^shift / s)) + 1/2) for j < 7, corr[7] = 0
+ * and with shift < 0 the smallest shift at which s log1p(exp(-7 2^shift / s)) < 1.  At 8 steps per unit:
+ * shift 3 and {9, 6, 4, 3, 2, 1, 1, 0}.  TD_EINVAL: a null output, steps_per_unit outside (0, 32], or a rule
+ * that gives an entry above 63 or a shift above 8.
+ */
+typedef struct td_fixed_maxstar_params {
+    int shift;          /* bucket width 2^shift, 0 .. 8 */
+    uint8_t corr[8];    /* correction of bucket j, each 0 .. 63, corr[7] == 0 */
+} td_fixed_maxstar_params;
+int td_set_fixed_maxstar(td_handle* h, const td_fixed_maxstar_params* m);   /* NULL: off (Max-Log-MAP) */
+int td_fixed_maxstar_table(double steps_per_unit, int shift /* < 0: choose */, td_fixed_maxstar_params* out);
+/*
  * Per-codeword early termination of the fixed-point decoder: the third sibling of td_set_early_stop and
  * td_set_window_stop, with their two rules, td_stop_params, frozen-row convention and iters_used output,
  * judged on the fixed decode's own rows.  Off by default; with it off a fixed decode launches the

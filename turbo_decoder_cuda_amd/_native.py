@@ -31,6 +31,7 @@ EXPORTS = (
     "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
     "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
     "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window", "td_set_fixed_window_stop",
+    "td_set_fixed_maxstar", "td_fixed_maxstar_table",
 )
 
 
@@ -56,6 +57,10 @@ class TdFixedParams(C.Structure):
 
 class TdFixedWindowParams(C.Structure):
     _fields_ = [("window", C.c_int), ("overlap", C.c_int)]
+
+
+class TdFixedMaxstarParams(C.Structure):
+    _fields_ = [("shift", C.c_int), ("corr", C.c_uint8 * 8)]
 
 
 class TurboError(RuntimeError):
@@ -135,6 +140,9 @@ def lib() -> C.CDLL:
         L.td_set_fixed_window.argtypes = [P, C.POINTER(TdFixedWindowParams)]
     if hasattr(L, "td_set_fixed_window_stop"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_set_fixed_window_stop.argtypes = [P, C.POINTER(TdStopParams)]
+    if hasattr(L, "td_set_fixed_maxstar"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_set_fixed_maxstar.argtypes = [P, C.POINTER(TdFixedMaxstarParams)]
+        L.td_fixed_maxstar_table.argtypes = [C.c_double, I, C.POINTER(TdFixedMaxstarParams)]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -127,6 +127,9 @@ struct td_handle {
     bool rm_set = false;
     // the fixed-point decoder (TD_FIXED): the extrinsic's clamp and scale (td_set_fixed)
     td_fixed_params fxp{255, 3};
+    // the fixed-point decoder's correction table (td_set_fixed_maxstar): off = Max-Log-MAP
+    bool fms_on = false;
+    td_fixed_maxstar_params fms{};
     // early termination of the fixed-point decoder (td_set_fixed_stop): rule 0 = off; its CRC table is d_crc
     td_stop_params fstop{TD_STOP_NONE, 1, 0};
     // the fixed-point decoder's sub-block schedule (td_set_fixed_window): window 0 = the exact schedule
@@ -717,6 +720,16 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         ev = h->ev[h->nev].data();
         TD_HIP(hipEventRecord(ev[0], st));
     }
+    // the table travels as kernel arguments: nothing on the device to allocate or to copy
+    td::fx::MaxStar ms{};
+    if (h->fms_on) {
+        for (int j = 0; j < 4; ++j) {
+            ms.lo |= (uint32_t)h->fms.corr[j] << (8 * j);
+            ms.hi |= (uint32_t)h->fms.corr[4 + j] << (8 * j);
+        }
+        ms.shift = h->fms.shift;
+    }
+    const td::fx::MaxStar* m = h->fms_on ? &ms : nullptr;
     hipError_t e = td::launch_fixed_demux(a, static_cast<const int8_t*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
@@ -727,7 +740,7 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         s.first = std::max(hda ? 2 : 1, h->fstop.min_iters);
         s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
         s.used = reinterpret_cast<int32_t*>(ws + c.used);
-        e = td::launch_fixed_turbo_stop(a, s, d_bits, d_iters, st);
+        e = td::launch_fixed_turbo_stop(a, s, m, d_bits, d_iters, st);
     } else if (h->fwin.window && h->fwstop.rule != TD_STOP_NONE) {
         const bool hda = h->fwstop.rule == TD_STOP_HDA;
         td::fx::FxStop s{};
@@ -735,14 +748,14 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         s.first = std::max(hda ? 2 : 1, h->fwstop.min_iters);
         s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
         s.used = reinterpret_cast<int32_t*>(ws + c.used);
-        e = td::launch_fixed_window_stop(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, s,
+        e = td::launch_fixed_window_stop(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, s, m,
                                          reinterpret_cast<uint32_t*>(ws + c.ev),
                                          reinterpret_cast<uint16_t*>(ws + c.hist), d_bits, d_iters, st);
     } else {
         if (h->fwin.window)
-            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, d_bits, st);
+            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, m, d_bits, st);
         else
-            e = td::launch_fixed_turbo(a, d_bits, st);
+            e = td::launch_fixed_turbo(a, m, d_bits, st);
         if (e == hipSuccess && d_iters)   // no rule (td_set_fixed_stop): every codeword takes them all
             e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
     }
@@ -1244,6 +1257,46 @@ int td_set_fixed(td_handle* h, const td_fixed_params* f)
     if (f->ext_scale_q < 1 || f->ext_scale_q > 4)
         return fail(TD_EINVAL, "td_set_fixed: ext_scale_q must be in [1, 4] (quarters; 4 = no scaling)");
     h->fxp = *f;
+    return TD_OK;
+}
+
+int td_set_fixed_maxstar(td_handle* h, const td_fixed_maxstar_params* m)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed_maxstar: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_maxstar: the handle is not fixed-point (TD_FIXED)");
+    if (!m) {
+        h->fms_on = false;
+        return TD_OK;
+    }
+    if (m->shift < 0 || m->shift > 8) return fail(TD_EINVAL, "td_set_fixed_maxstar: shift must be in [0, 8]");
+    for (int j = 0; j < 8; ++j)
+        if (m->corr[j] > 63) return fail(TD_EINVAL, "td_set_fixed_maxstar: every entry of corr must be in [0, 63]");
+    if (m->corr[7] != 0) return fail(TD_EINVAL, "td_set_fixed_maxstar: corr[7] must be 0");
+    h->fms = *m;
+    h->fms_on = true;
+    return TD_OK;
+}
+
+int td_fixed_maxstar_table(double steps_per_unit, int shift, td_fixed_maxstar_params* out)
+{
+    if (!out) return fail(TD_EINVAL, "td_fixed_maxstar_table: null output");
+    if (!(steps_per_unit > 0.0 && steps_per_unit <= 32.0))
+        return fail(TD_EINVAL, "td_fixed_maxstar_table: steps_per_unit must be in (0, 32]");
+    const double s = 2.0 * steps_per_unit;   // metric steps per nat
+    if (shift < 0) {
+        shift = 0;
+        while (shift <= 8 && !(s * std::log1p(std::exp(-7.0 * std::ldexp(1.0, shift) / s)) < 1.0)) ++shift;
+    }
+    if (shift > 8) return fail(TD_EINVAL, "td_fixed_maxstar_table: the rule gives a shift above 8");
+    td_fixed_maxstar_params t{};
+    t.shift = shift;
+    for (int j = 0; j < 7; ++j) {
+        const double c = std::floor(s * std::log1p(std::exp(-(j + 0.5) * std::ldexp(1.0, shift) / s)) + 0.5);
+        if (c > 63.0) return fail(TD_EINVAL, "td_fixed_maxstar_table: the rule gives an entry above 63");
+        t.corr[j] = (uint8_t)c;
+    }
+    t.corr[7] = 0;
+    *out = t;
     return TD_OK;
 }
 

@@ -51,22 +51,25 @@ inline FxCarve fx_carve(int B, int K, int iters)
 // links, and the fixed entry points then fail with TD_EHIP.  libturbo_mi355x.so always has them.
 // d_q [B][3K+12] int8 -> xs / xp1 / xp2 of the workspace (-128 read as -127, the padding zeroed)
 __attribute__((weak)) hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st);
+// The four decodes below take m, td_set_fixed_maxstar's table or null: with a table they launch the kernels
+// instantiated with fx::MaxStar, without one the Max-Log-MAP kernels.
 // all iterations of all codewords, then bitsT -> d_bits ([B][K] or [B][iters][K])
-__attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t st);
+__attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, const fx::MaxStar* m, uint8_t* d_bits,
+                                                    hipStream_t st);
 // the same with early termination: a codeword's rows past its stop are copies of its stop row, d_bits
 // without all_iters is its stop row, and d_iters (nullable, [B]) gets s.used
-__attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uint8_t* d_bits,
-                                                         int32_t* d_iters, hipStream_t st);
+__attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, const fx::MaxStar* m,
+                                                         uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
 // the sub-block schedule (td_set_fixed_window): a launch per SISO and iteration on st, grid (Bp / kFxLanes) x
 // sub-blocks, then bitsT -> d_bits as launch_fixed_turbo
-__attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8_t* d_bits,
-                                                     hipStream_t st);
+__attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m,
+                                                     uint8_t* d_bits, hipStream_t st);
 // the sub-block schedule with early termination (td_set_fixed_window_stop): s.used is reset on st, then per
 // iteration SISO1, SISO2 and the judge, then the frozen rows and d_iters as launch_fixed_turbo_stop; d_ev and
 // d_hist are the carve's ev and hist
 __attribute__((weak)) hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s,
-                                                          uint32_t* d_ev, uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters,
-                                                          hipStream_t st);
+                                                          const fx::MaxStar* m, uint32_t* d_ev, uint16_t* d_hist,
+                                                          uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

@@ -1,6 +1,6 @@
 // td_fixed.hip -- the fixed-point decoder (TD_FIXED) on gfx950: int8 channel LLRs in, integer
-// Max-Log-MAP, int16 extrinsics, uint8 decisions.  The arithmetic is td_fixed_core.h's; here are the
-// kernels around it.
+// Max-Log-MAP (or, with td_set_fixed_maxstar's table, integer log-MAP), int16 extrinsics, uint8 decisions.
+// The arithmetic is td_fixed_core.h's; here are the kernels around it.
 //
 //   fx_demux_kernel    q [B][3K+12] -> xs, xp1, xp2 [row][Bp]: a 64 x 64 byte transpose through LDS, so
 //                      that both the reads (along the stream) and the writes (along the batch) are
@@ -25,6 +25,11 @@
 //                      the next iteration's HDA comparison, every 16-step window's decisions packed) and the
 //                      judge, a launch of its own after SISO2's, folds it and stops the codeword; then
 //                      fx_bits_stop_kernel.
+//   fx_turbo_maxstar_kernel, fx_turbo_stop_maxstar_kernel, fx_window_siso_maxstar_kernel,
+//   fx_window_siso_stop_maxstar_kernel  the decoding kernels above with td_set_fixed_maxstar's table: the lane
+//                      code instantiated with fx::MaxStar for fx::MaxLog, the table's two words and its shift
+//                      as kernel arguments (scalar registers).  Launched only while a table is set; without
+//                      one a decode launches the kernels above, which do not change.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
 #include <hip/hip_runtime.h>
 
@@ -160,6 +165,33 @@ __global__ __launch_bounds__(kTileThreads) void fx_window_judge_kernel(fx::FxArg
     fx::window_judge(p, s, ev, nS, (size_t)blockIdx.x * kTileThreads + threadIdx.x, it);
 }
 
+// The four decoding kernels with the correction table (td_set_fixed_maxstar): the same grids and arguments,
+// and m, the same in every lane.
+__global__ __launch_bounds__(kFxLanes) void fx_turbo_maxstar_kernel(fx::FxArgs p, fx::MaxStar m)
+{
+    fx::decode_codeword(p, blockIdx.x * kFxLanes + threadIdx.x, m);
+}
+
+__global__ __launch_bounds__(kFxLanes) void fx_turbo_stop_maxstar_kernel(fx::FxArgs p, fx::FxStop s, fx::MaxStar m)
+{
+    fx::decode_codeword_stop(p, s, blockIdx.x * kFxLanes + threadIdx.x, m);
+}
+
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_maxstar_kernel(fx::FxArgs p, fx::FxWindow w, fx::MaxStar m,
+                                                                           int it)
+{
+    fx::siso_window_pass<DEC>(p, w, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
+}
+
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_maxstar_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
+                                                                                fx::MaxStar m, uint32_t* __restrict__ ev,
+                                                                                uint16_t* __restrict__ hist, int it)
+{
+    fx::siso_window_stop<DEC>(p, w, s, ev, hist, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
+}
+
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
 // addition: no atomics, the same bytes on every run.
 template <bool ACC>
@@ -201,9 +233,12 @@ hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t st)
+hipError_t launch_fixed_turbo(const fx::FxArgs& p, const fx::MaxStar* m, uint8_t* d_bits, hipStream_t st)
 {
-    hipLaunchKernelGGL(fx_turbo_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p);
+    if (m)
+        hipLaunchKernelGGL(fx_turbo_maxstar_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, *m);
+    else
+        hipLaunchKernelGGL(fx_turbo_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int rows = p.all_iters ? p.iters : 1;
@@ -212,10 +247,13 @@ hipError_t launch_fixed_turbo(const fx::FxArgs& p, uint8_t* d_bits, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uint8_t* d_bits, int32_t* d_iters,
-                                   hipStream_t st)
+hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, const fx::MaxStar* m, uint8_t* d_bits,
+                                   int32_t* d_iters, hipStream_t st)
 {
-    hipLaunchKernelGGL(fx_turbo_stop_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s);
+    if (m)
+        hipLaunchKernelGGL(fx_turbo_stop_maxstar_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s, *m);
+    else
+        hipLaunchKernelGGL(fx_turbo_stop_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int rows = p.all_iters ? p.iters : 1;
@@ -225,12 +263,18 @@ hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, uin
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8_t* d_bits, hipStream_t st)
+hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m, uint8_t* d_bits,
+                               hipStream_t st)
 {
     const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)fx::window_blocks(p.L, w.window));
     for (int it = 0; it < p.iters; ++it) {
-        hipLaunchKernelGGL(fx_window_siso_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
-        hipLaunchKernelGGL(fx_window_siso_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+        if (m) {
+            hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
+            hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
+        } else {
+            hipLaunchKernelGGL(fx_window_siso_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+            hipLaunchKernelGGL(fx_window_siso_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -240,8 +284,8 @@ hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, uint8
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s, uint32_t* d_ev,
-                                    uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters, hipStream_t st)
+hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s, const fx::MaxStar* m,
+                                    uint32_t* d_ev, uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters, hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(s.used, 0, p.Bp * sizeof(int32_t), st);   // every codeword runs
     if (e != hipSuccess) return e;
@@ -249,8 +293,13 @@ hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, 
     const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)nS);
     const dim3 jgrid((unsigned)((p.Bp + kTileThreads - 1) / kTileThreads));
     for (int it = 0; it < p.iters; ++it) {
-        hipLaunchKernelGGL(fx_window_siso_stop_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
-        hipLaunchKernelGGL(fx_window_siso_stop_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
+        if (m) {
+            hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
+            hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
+        } else {
+            hipLaunchKernelGGL(fx_window_siso_stop_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
+            hipLaunchKernelGGL(fx_window_siso_stop_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
+        }
         hipLaunchKernelGGL(fx_window_judge_kernel, jgrid, dim3(kTileThreads), 0, st, p, s, d_ev, nS, it);
     }
     e = hipGetLastError();

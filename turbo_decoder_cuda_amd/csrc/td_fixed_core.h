@@ -11,7 +11,8 @@
 // for beta, and |alpha + gamma + beta| < 2^24.  An unreachable state is kNeg = -2^28: sums of up to two
 // of them and a reachable part stay above -2^30, so nothing wraps, and no sum that contains one
 // reaches a reachable path's (>= -2^24).  Nothing saturates except the two clamps of the contract
-// (the input's -128 -> -127 and the extrinsic's +-le_max).
+// (the input's -128 -> -127 and the extrinsic's +-le_max).  With td_set_fixed_maxstar's correction table
+// (MaxStar below) a step adds up to 63 more: the same bounds hold, as worked out there.
 #pragma once
 
 #include <stdint.h>
@@ -74,6 +75,51 @@ TDF_HD int ext_f(int r, int le_max, int scale_q)
 
 TDF_HD int imax(int a, int b) { return a > b ? a : b; }
 
+// The max of the recursions and of the two folds of Lambda, a compile-time choice through the lane code.
+// MaxLog is the contract's plain max (Max-Log-MAP).  MaxStar is td_set_fixed_maxstar's integer log-MAP:
+//   maxs(a, b) = max(a, b) + corr[min(|a - b| >> shift, 7)],  corr[j] <= 63, corr[7] == 0
+// with the eight entries packed a byte each into two words (lo: buckets 0..3, hi: 4..7), next to FxArgs
+// and not in it, as FxStop and FxWindow are.  The words and the shift are kernel arguments, the same in
+// every lane: they stay in scalar registers and the entry is one byte permute of them -- no LDS, no memory.
+// maxs rounds, so it is not associative: the order of the operands and of the folds below is the
+// contract's (include/turbo_mi355x.h).
+//
+// Bounds with a table.  A step adds at most 509 + 63 to a metric, so after i steps |alpha| <=
+// 572 * 10003 < 2^23 (5.73e6 < 8.39e6), the same for beta; a Lambda term is alpha + gamma + beta plus the
+// seven corrections of its fold, |.| <= 2 * 572 * 10003 + 509 + 441 < 2^24.  A warm-up from equal metrics
+// (all 0) is inside the same bounds: its metrics are at most 572 per step from 0.  corr[7] == 0 makes
+// maxs of a reachable sum (>= -2^24) and one that holds kNeg (<= kNeg + 2^24, more than 7 * 2^8 below it)
+// the reachable sum exactly; maxs of two sums that hold kNeg adds at most 63 to one of them, and a fold
+// at most 441: still above -2^30 and below every reachable sum.  So int32 and kNeg stay as they are.
+struct MaxLog {
+    static constexpr bool kTable = false;
+    TDF_HD int operator()(int a, int b) const { return imax(a, b); }
+};
+
+struct MaxStar {
+    static constexpr bool kTable = true;
+    uint32_t lo, hi;      // corr[0..3], corr[4..7], entry j in byte j & 3
+    int shift;            // bucket width 2^shift, 0 .. 8
+    TDF_HD int operator()(int a, int b) const
+    {
+        const int mx = a > b ? a : b, mn = a > b ? b : a;
+        unsigned j = (unsigned)(mx - mn) >> shift;   // the difference of two int32 metrics of the bounds above: no wrap
+        j = j < 7u ? j : 7u;
+#if defined(__HIP_DEVICE_COMPILE__)
+        return mx + (int)(__builtin_amdgcn_perm(hi, lo, j) & 0xffu);   // byte j of hi:lo
+#else
+        return mx + (int)(((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xffu);
+#endif
+    }
+};
+
+// LLR = Lambda / 2 towards zero, as f truncates.  Max-Log-MAP's Lambda is even: there it is the shift.
+template <class M>
+TDF_HD int half_lambda(int lam)
+{
+    return M::kTable ? lam / 2 : lam >> 1;
+}
+
 // An interleaver entry.  The tables do not change while a decode runs and the index is the same for
 // the whole wave, so the device reads them through the constant address space: a scalar load, whose
 // result (a row number) stays in a scalar register and makes the row's address a scalar too.
@@ -97,14 +143,15 @@ TDF_HD void gammas(int S, int P, int (&c)[4])
 }
 constexpr int gsel(int s, int u) { return 2 * u + (parity(s, u) > 0 ? 1 : 0); }
 
-TDF_HD void alpha_step(const int (&a)[8], int S, int P, int (&n)[8])
+template <class M = MaxLog>
+TDF_HD void alpha_step(const int (&a)[8], int S, int P, int (&n)[8], const M& mx = M())
 {
     int c[4];
     gammas(S, P, c);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int p0 = prev_state(j, 0), p1 = prev_state(j, 1);
-        n[j] = imax(a[p0] + c[gsel(p0, 0)], a[p1] + c[gsel(p1, 1)]);
+        n[j] = mx(a[p0] + c[gsel(p0, 0)], a[p1] + c[gsel(p1, 1)]);
     }
 }
 
@@ -130,7 +177,7 @@ TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
     }
 }
 
-// One terminated Max-Log-MAP pass of codeword b with everything that follows it in the iteration:
+// One terminated pass of codeword b (Max-Log-MAP, or log-MAP with mx a MaxStar) with everything that follows it in the iteration:
 // the extrinsic (ext12 / ext21 and the caller's Le), and after SISO2 the hard decisions.
 //
 // STOP (the stopping decoder, sp its rule): SISO2 writes row `it` of bitsT in every iteration and returns
@@ -143,8 +190,8 @@ TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
 // bit a step into a register, and compared with the window's new bits at its end.  CRC: the lane XORs
 // in the syndrome of every 1 bit, from a table in the same order.  The state is the evidence and two
 // bit masks; the previous row stays in the workspace.  Iterations before sp->first are not judged.
-template <int DEC, bool STOP>
-TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
+template <int DEC, bool STOP, class M = MaxLog>
+TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it, const M& mx = M())
 {
     const int L = p.L, K = p.K;
     const int nW = (L + kW - 1) / kW;
@@ -165,7 +212,7 @@ TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
 #pragma unroll
             for (int t = 0; t < kW; ++t) {
                 int n[8];
-                alpha_step(a, S[t], P[t], n);
+                alpha_step(a, S[t], P[t], n, mx);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) a[s] = n[s];
             }
@@ -203,7 +250,7 @@ TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
 #pragma unroll
         for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
 #pragma unroll
-        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1]);
+        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1], mx);
 #pragma unroll
         for (int t = kW - 1; t >= 0; --t) {
             const int i = i0 + t;
@@ -219,10 +266,10 @@ TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
                 int m0 = A[t][0] + e0[0], m1 = A[t][0] + e1[0];
 #pragma unroll
                 for (int s = 1; s < 8; ++s) {
-                    m0 = imax(m0, A[t][s] + e0[s]);
-                    m1 = imax(m1, A[t][s] + e1[s]);
+                    m0 = mx(m0, A[t][s] + e0[s]);
+                    m1 = mx(m1, A[t][s] + e1[s]);
                 }
-                const int llr = (m1 - m0) >> 1;   // Lambda is even
+                const int llr = half_lambda<M>(m1 - m0);
                 const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
                 if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
                 if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
@@ -240,7 +287,7 @@ TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
                     }
                 }
 #pragma unroll
-                for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
+                for (int s = 0; s < 8; ++s) bt[s] = mx(e0[s], e1[s]);
             }
         }
         acc |= (int)(was ^ now);
@@ -248,17 +295,12 @@ TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it)
     return acc;
 }
 
-template <int DEC>
-TDF_HD void siso(const FxArgs& p, size_t b, int it)
-{
-    siso_pass<DEC, false>(p, nullptr, b, it);
-}
-
-TDF_HD void decode_codeword(const FxArgs& p, size_t b)
+template <class M = MaxLog>
+TDF_HD void decode_codeword(const FxArgs& p, size_t b, const M& mx = M())
 {
     for (int it = 0; it < p.iters; ++it) {
-        siso<0>(p, b, it);
-        siso<1>(p, b, it);
+        siso_pass<0, false>(p, nullptr, b, it, mx);
+        siso_pass<1, false>(p, nullptr, b, it, mx);
     }
 }
 
@@ -271,13 +313,14 @@ struct FxWindow {
 constexpr int window_blocks(int L, int window) { return L / window > 1 ? L / window : 1; }
 
 // One beta step backwards over position i's branch metrics, without an output (the warm-up).
-TDF_HD void beta_step(int (&bt)[8], int S, int P)
+template <class M = MaxLog>
+TDF_HD void beta_step(int (&bt)[8], int S, int P, const M& mx = M())
 {
     int c[4];
     gammas(S, P, c);
     int n[8];
 #pragma unroll
-    for (int s = 0; s < 8; ++s) n[s] = imax(c[gsel(s, 0)] + bt[next_state(s, 0)], c[gsel(s, 1)] + bt[next_state(s, 1)]);
+    for (int s = 0; s < 8; ++s) n[s] = mx(c[gsel(s, 0)] + bt[next_state(s, 0)], c[gsel(s, 1)] + bt[next_state(s, 1)]);
 #pragma unroll
     for (int s = 0; s < 8; ++s) bt[s] = n[s];
 }
@@ -304,9 +347,9 @@ TDF_HD void beta_step(int (&bt)[8], int S, int P)
 // previous bits are one 16-bit load together with the window's inputs; the slot is the lane's own, read
 // before it is written.  The codeword's evidence is the fold of its sub-blocks' words, which the launch
 // after SISO2's makes (fx_window_judge_kernel): no atomics, and no launch reads a word of ev that it writes.
-template <int DEC, bool STOP>
+template <int DEC, bool STOP, class M = MaxLog>
 TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop* sp, uint32_t* ev, uint16_t* hist,
-                               size_t b, int it, int sb)
+                               size_t b, int it, int sb, const M& mx = M())
 {
     const int L = p.L, K = p.K, W = wn.window;
     const int nS = window_blocks(L, W);
@@ -328,7 +371,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
 #pragma unroll
             for (int t = 0; t < kW; ++t) {
                 int n[8];
-                alpha_step(a, S[t], P[t], n);
+                alpha_step(a, S[t], P[t], n, mx);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) a[s] = n[s];
             }
@@ -336,7 +379,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
         for (; i < start; ++i) {
             int S, P, n[8];
             load_step<DEC>(p, b, it, i, S, P);
-            alpha_step(a, S, P, n);
+            alpha_step(a, S, P, n, mx);
 #pragma unroll
             for (int s = 0; s < 8; ++s) a[s] = n[s];
         }
@@ -350,7 +393,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
 #pragma unroll
             for (int t = 0; t < kW; ++t) {
                 int n[8];
-                alpha_step(a, S[t], P[t], n);
+                alpha_step(a, S[t], P[t], n, mx);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) a[s] = n[s];
             }
@@ -367,12 +410,12 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
 #pragma unroll
             for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i - 1 - t, S[t], P[t]);
 #pragma unroll
-            for (int t = 0; t < kW; ++t) beta_step(bt, S[t], P[t]);
+            for (int t = 0; t < kW; ++t) beta_step(bt, S[t], P[t], mx);
         }
         for (; i > end; --i) {
             int S, P;
             load_step<DEC>(p, b, it, i - 1, S, P);
-            beta_step(bt, S, P);
+            beta_step(bt, S, P, mx);
         }
     }
 
@@ -395,7 +438,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
 #pragma unroll
         for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
 #pragma unroll
-        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1]);
+        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1], mx);
 #pragma unroll
         for (int t = kW - 1; t >= 0; --t) {
             const int i = i0 + t;
@@ -411,10 +454,10 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
                 int m0 = A[t][0] + e0[0], m1 = A[t][0] + e1[0];
 #pragma unroll
                 for (int s = 1; s < 8; ++s) {
-                    m0 = imax(m0, A[t][s] + e0[s]);
-                    m1 = imax(m1, A[t][s] + e1[s]);
+                    m0 = mx(m0, A[t][s] + e0[s]);
+                    m1 = mx(m1, A[t][s] + e1[s]);
                 }
-                const int llr = (m1 - m0) >> 1;   // Lambda is even
+                const int llr = half_lambda<M>(m1 - m0);
                 const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
                 if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
                 if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
@@ -430,7 +473,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
                         acc ^= -bit & table_entry(sp->syn, i);
                 }
 #pragma unroll
-                for (int s = 0; s < 8; ++s) bt[s] = imax(e0[s], e1[s]);
+                for (int s = 0; s < 8; ++s) bt[s] = mx(e0[s], e1[s]);
             }
         }
         if (STOP && hda) {
@@ -442,10 +485,10 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
     if (STOP && judge) ev[(size_t)sb * p.Bp + b] = (uint32_t)acc;
 }
 
-template <int DEC>
-TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb)
+template <int DEC, class M = MaxLog>
+TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb, const M& mx = M())
 {
-    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, b, it, sb);
+    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, b, it, sb, mx);
 }
 
 // true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
@@ -464,14 +507,15 @@ TDF_HD bool any_lane(bool run)
 // that the transpose back makes (fx_bits_stop_kernel).  The loop's exit is the wave's: it leaves once
 // none of its lanes runs, so `it` and every table index stay uniform.  A lane of the padding never
 // runs (its zeros decode to an all-ones row, which no CRC passes).
-TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b)
+template <class M = MaxLog>
+TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b, const M& mx = M())
 {
     bool run = b < (size_t)p.B;
     int used = p.iters;
     for (int it = 0; it < p.iters; ++it) {
         if (run) {
-            siso_pass<0, true>(p, &s, b, it);
-            const int acc = siso_pass<1, true>(p, &s, b, it);
+            siso_pass<0, true>(p, &s, b, it, mx);
+            const int acc = siso_pass<1, true>(p, &s, b, it, mx);
             if (it + 1 >= s.first && acc == 0) {
                 used = it + 1;
                 run = false;
@@ -487,13 +531,13 @@ TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b)
 // iterations.  A wave none of whose lanes runs returns on the ballot -- where the time is saved -- and a
 // stopped lane of a running wave is skipped by a branch and writes nothing; a lane of the padding never
 // runs.  sb must be the same in every lane of a wave.
-template <int DEC>
+template <int DEC, class M = MaxLog>
 TDF_HD void siso_window_stop(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist, size_t b,
-                             int it, int sb)
+                             int it, int sb, const M& mx = M())
 {
     const bool run = b < (size_t)p.B && s.used[b] == 0;
     if (!any_lane(run)) return;
-    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, b, it, sb);
+    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, b, it, sb, mx);
 }
 
 // The decision after SISO2's launch of iteration `it`, one call per codeword: a running codeword stops

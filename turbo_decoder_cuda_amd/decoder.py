@@ -28,6 +28,19 @@ _NP_DT = {"f64": np.float64, "f32": np.float32, "fixed": np.int8}
 _STOP_RULES = {None: N.TD_STOP_NONE, "hda": N.TD_STOP_HDA, "crc": N.TD_STOP_CRC}
 
 
+def _maxstar_table(steps_per_unit, shift=None):
+    m = N.TdFixedMaxstarParams()
+    N.check(N.lib().td_fixed_maxstar_table(float(steps_per_unit), -1 if shift is None else int(shift), C.byref(m)))
+    return m
+
+
+def fixed_maxstar_table(steps_per_unit: float, shift=None):
+    """(shift, corr) of td_fixed_maxstar_table: the integer log-MAP correction table for LLRs quantised
+    at steps_per_unit steps per unit; shift=None chooses the bucket width.  Host only."""
+    m = _maxstar_table(steps_per_unit, shift)
+    return int(m.shift), tuple(int(v) for v in m.corr)
+
+
 def stream_length(K: int) -> int:
     """3K+12: the coded stream length TurboDecoding takes (main.cpp:221)."""
     return 3 * K + 12
@@ -122,6 +135,26 @@ class TurboCodec:
         N.check(N.lib().td_set_fixed_window(self._h, C.byref(w)))
         if not int(window) and self._window_stop:   # td_set_fixed_window(0) clears the sub-block schedule's rule
             self.early_stop, self._window_stop = None, False
+
+    def set_fixed_maxstar(self, steps_per_unit=8.0, shift=None, table=None) -> None:
+        """Integer log-MAP on the fixed-point decoder (td_set_fixed_maxstar; precision="fixed" only): every
+        max becomes max + corr[min(|a - b| >> shift, 7)].  The table is fixed_maxstar_table(steps_per_unit,
+        shift) -- for LLRs quantised at steps_per_unit steps per unit -- or table=(shift, corr) as is (eight
+        entries 0 .. 63, the last 0).  set_fixed_maxstar(None) turns it off (Max-Log-MAP).  It applies to
+        every fixed schedule and survives the other setters.  Log-MAP wants set_fixed(255, 4): the default
+        3/4 scale compensates Max-Log-MAP."""
+        if steps_per_unit is None and table is None:
+            N.check(N.lib().td_set_fixed_maxstar(self._h, None))
+            return
+        if table is not None:
+            sh, corr = table
+            corr = [int(v) for v in corr]
+            if len(corr) != 8 or any(not 0 <= v <= 255 for v in corr):
+                raise ValueError("table = (shift, corr): corr is eight entries")
+            m = N.TdFixedMaxstarParams(int(sh), (C.c_uint8 * 8)(*corr))
+        else:
+            m = _maxstar_table(steps_per_unit, shift)
+        N.check(N.lib().td_set_fixed_maxstar(self._h, C.byref(m)))
 
     def set_window_maxstar(self, exact: bool) -> None:
         """max* of the windowed log-MAP schedule (td_set_window_maxstar): exact=False the one-read
