@@ -344,9 +344,9 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s);
  *                 td_set_fixed setting and the hard bit at the sub-block's own positions, from its own
  *                 alpha and beta: exactly the TD_FIXED contract's branch metric, plain max and f.
  * The iteration (SISO1 over all sub-blocks, then SISO2 over all sub-blocks, serially), the hard decision
- * and the layouts of d_bits and d_le are the TD_FIXED contract's.  No next-iteration initialisation, no
- * concurrent SISOs and no extra extrinsic scale (td_window_params' nii, concurrent, ext_scale have no
- * counterpart here).  The state metrics are wide enough that nothing saturates but the contract's two
+ * and the layouts of d_bits and d_le are the TD_FIXED contract's.  No concurrent SISOs and no extra
+ * extrinsic scale (td_window_params' concurrent and ext_scale have no counterpart here; its nii is
+ * td_set_fixed_window_nii below, off by default).  The state metrics are wide enough that nothing saturates but the contract's two
  * clamps; the result is the one that un-normalised integers of unlimited width give (max-log does not
  * change when a constant is added to all states, so an implementation may normalise or not).  Every
  * value is therefore defined bit for bit (tests/fixed_window_ref.py restates it).
@@ -371,6 +371,43 @@ typedef struct td_fixed_window_params {
     int overlap;   /* warm-up positions on each side, 0 .. 3 * window */
 } td_fixed_window_params;
 int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w);
+/*
+ * Next-iteration initialisation (NII) of the sub-block schedule: the integer counterpart of
+ * td_window_params.nii, which lets a smaller overlap do (profiles/fixed/window_nii_ber.json).  Off by
+ * default; with it off a decode launches the kernels it always did.  With it on the schedule is
+ * td_set_fixed_window's in every detail except the start vectors of warm-ups that do not begin at a trellis
+ * end, in iterations n >= 2 (1-based).  For SISO d in {1, 2}, sub-block s covering [s W, e), a_from =
+ * s W - overlap and b_from = e + overlap:
+ *   alpha   if a_from > 0, starts from A[a_from] of SISO d in iteration n - 1, where A[p] is the alpha
+ *           vector before step p as computed by the sub-block that outputs position p - 1, sub-block
+ *           (p - 1) / W (the neighbouring chain that has run longest, not another sub-block's warm-up).
+ *   beta    if b_from < L, starts from B[b_from] of SISO d in iteration n - 1, where B[p] is the beta
+ *           vector after the backward step over position p as computed by the sub-block that outputs
+ *           position p, sub-block min(p / W, nS - 1).
+ * Iteration 1 starts from equal metrics, and a warm-up that reaches a trellis end starts terminated, as
+ * without NII.  Both max and td_set_fixed_maxstar's maxs are unchanged by a constant added to all eight
+ * states, so A and B are defined up to one constant per vector: the outputs are those of un-normalised
+ * integers of unlimited width (the implementation stores the vectors relative to their maximum, an
+ * unreachable state staying unreachable), and rows of every iteration and every Le stay defined bit for
+ * bit (tests/fixed_window_nii_ref.py restates it).  Consequences: row 1 and Le of iteration 1 equal the NII-off
+ * decode's; with overlap >= L or nS = 1 the decode is still the exact fixed decode; a codeword's result
+ * does not depend on its lane, wave, batch or the batch size, nor on what the handle decoded before
+ * (the state is never read in iteration 1, so a graph replay repeats the bytes); the two SISOs keep
+ * separate state.
+ * Valid on a TD_FIXED handle with a window set, otherwise TD_EINVAL.  With NII on the overlap must be a
+ * multiple of 16 (the vectors are then taken between the 16-step windows of the kernel): turning NII on
+ * with another overlap is TD_EINVAL, and so is td_set_fixed_window with such an overlap while NII is on.  A
+ * failed call changes nothing.  NII survives td_set_fixed, td_set_fixed_maxstar, td_set_fixed_window_stop and a
+ * later td_set_fixed_window with window > 0; td_set_fixed_window(NULL or window 0) clears it.  It works with
+ * td_set_fixed_maxstar's table and with td_set_fixed_window_stop's rules, which judge the NII decode's own
+ * rows (min_iters == iterations still reproduces the rule-off NII decode byte for byte).
+ * The state is 128 bytes per sub-block and codeword behind the workspace, carved only while NII is on
+ * and sized for the current window (12 % more at K = 6144, window 64, 8 iterations): a handle that never
+ * turns NII on keeps the workspace it had.  So td_reserve belongs after td_set_fixed_window_nii (and after
+ * td_set_fixed_window): a decode after it allocates nothing and may be captured into a hipGraph; without it
+ * a decode grows the workspace on demand, as it does for B.
+ */
+int td_set_fixed_window_nii(td_handle* h, int on);   /* 0 = off (default) */
 /*
  * Per-codeword early termination of the fixed-point decoder's sub-block schedule: the fourth sibling of
  * td_set_early_stop, td_set_window_stop and td_set_fixed_stop, with their two rules, td_stop_params,

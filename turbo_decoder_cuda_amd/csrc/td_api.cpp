@@ -137,6 +137,9 @@ struct td_handle {
     // early termination of the sub-block schedule (td_set_fixed_window_stop): rule 0 = off; its CRC table is d_crc
     // (a fixed handle has a rule of one kind at most: td_set_fixed_stop's needs window 0, this one a window)
     td_stop_params fwstop{TD_STOP_NONE, 1, 0};
+    // next-iteration initialisation of the sub-block schedule (td_set_fixed_window_nii): its state follows the
+    // workspace's carve while it is on
+    bool fnii = false;
 };
 
 namespace td {
@@ -657,7 +660,8 @@ int not_fixed(const td_handle* h, const char* who)
 // the fixed-point decoder's workspace for B codewords: a plain allocation, grown and never shrunk
 int ensure_fixed_ws(td_handle* h, int B)
 {
-    const td::FxCarve c = td::fx_carve(B, h->p.K, h->p.iterations);
+    td::FxCarve c = td::fx_carve(B, h->p.K, h->p.iterations);
+    if (h->fnii) c.total += td::fx_nii_bytes(B, h->p.K, h->fwin.window);   // sized for the current window's sub-blocks
     if (c.total <= h->ws_bytes) return TD_OK;
     if (h->d_ws) {
         TD_HIP(hipDeviceSynchronize());
@@ -730,6 +734,7 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         ms.shift = h->fms.shift;
     }
     const td::fx::MaxStar* m = h->fms_on ? &ms : nullptr;
+    uint32_t* d_nii = h->fnii ? reinterpret_cast<uint32_t*>(ws + c.total) : nullptr;   // ensure_fixed_ws sized it
     hipError_t e = td::launch_fixed_demux(a, static_cast<const int8_t*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
@@ -750,10 +755,10 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
         s.used = reinterpret_cast<int32_t*>(ws + c.used);
         e = td::launch_fixed_window_stop(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, s, m,
                                          reinterpret_cast<uint32_t*>(ws + c.ev),
-                                         reinterpret_cast<uint16_t*>(ws + c.hist), d_bits, d_iters, st);
+                                         reinterpret_cast<uint16_t*>(ws + c.hist), d_nii, d_bits, d_iters, st);
     } else {
         if (h->fwin.window)
-            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, m, d_bits, st);
+            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, m, d_nii, d_bits, st);
         else
             e = td::launch_fixed_turbo(a, m, d_bits, st);
         if (e == hipSuccess && d_iters)   // no rule (td_set_fixed_stop): every codeword takes them all
@@ -1307,6 +1312,7 @@ int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w)
     if (!w || w->window == 0) {
         h->fwin = td_fixed_window_params{0, 0};
         h->fwstop = td_stop_params{TD_STOP_NONE, 1, 0};   // the sub-block schedule's rule goes with it
+        h->fnii = false;                                  // and its next-iteration initialisation
         return TD_OK;
     }
     if (w->window < td::fx::kW || w->window % td::fx::kW)
@@ -1316,7 +1322,23 @@ int td_set_fixed_window(td_handle* h, const td_fixed_window_params* w)
     if (h->fstop.rule != TD_STOP_NONE)
         return fail(TD_EINVAL, "td_set_fixed_window: the TD_FIXED handle has an early-termination rule "
                                "(td_set_fixed_stop); turn it off first");
+    if (h->fnii && w->overlap % td::fx::kW)
+        return fail(TD_EINVAL, "td_set_fixed_window: with next-iteration initialisation on (td_set_fixed_window_nii) the "
+                               "overlap must be a multiple of 16");
     h->fwin = *w;
+    return TD_OK;
+}
+
+int td_set_fixed_window_nii(td_handle* h, int on)
+{
+    if (!h) return fail(TD_EINVAL, "td_set_fixed_window_nii: null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_window_nii: the handle is not fixed-point (TD_FIXED)");
+    if (!h->fwin.window)
+        return fail(TD_EINVAL, "td_set_fixed_window_nii: the TD_FIXED handle's schedule is not the sub-block one "
+                               "(td_set_fixed_window first)");
+    if (on && h->fwin.overlap % td::fx::kW)
+        return fail(TD_EINVAL, "td_set_fixed_window_nii: the overlap must be a multiple of 16 (td_set_fixed_window)");
+    h->fnii = on != 0;
     return TD_OK;
 }
 

@@ -47,6 +47,16 @@ inline FxCarve fx_carve(int B, int K, int iters)
     return c;
 }
 
+// The state of next-iteration initialisation (td_set_fixed_window_nii) follows the carve, and only while NII is
+// on: a handle that never turns it on keeps fx_carve's workspace byte for byte.  It is sized for the
+// current window's sub-blocks: 128 B per sub-block and codeword (two parities, two SISOs, alpha and beta,
+// eight int16), 12 % more at K = 6144, {64, g} and 8 iterations.
+inline size_t fx_nii_bytes(int B, int K, int window)
+{
+    const size_t Bp = ((size_t)B + kFxLanes - 1) / kFxLanes * kFxLanes;
+    return (fx::nii_words(K + 3, window, Bp) * 4 + 255) / 256 * 256;
+}
+
 // Weak references, like td_ratematch.h's: a host-only link of td_api.cpp without td_fixed.hip still
 // links, and the fixed entry points then fail with TD_EHIP.  libturbo_mi355x.so always has them.
 // d_q [B][3K+12] int8 -> xs / xp1 / xp2 of the workspace (-128 read as -127, the padding zeroed)
@@ -61,15 +71,17 @@ __attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, const f
 __attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, const fx::MaxStar* m,
                                                          uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
 // the sub-block schedule (td_set_fixed_window): a launch per SISO and iteration on st, grid (Bp / kFxLanes) x
-// sub-blocks, then bitsT -> d_bits as launch_fixed_turbo
+// sub-blocks, then bitsT -> d_bits as launch_fixed_turbo.  d_nii: the state of td_set_fixed_window_nii
+// (fx::nii_words words, right after the carve's total), or null: off, the kernels without it
 __attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m,
-                                                     uint8_t* d_bits, hipStream_t st);
+                                                     uint32_t* d_nii, uint8_t* d_bits, hipStream_t st);
 // the sub-block schedule with early termination (td_set_fixed_window_stop): s.used is reset on st, then per
 // iteration SISO1, SISO2 and the judge, then the frozen rows and d_iters as launch_fixed_turbo_stop; d_ev and
-// d_hist are the carve's ev and hist
+// d_hist are the carve's ev and hist, d_nii as for launch_fixed_window
 __attribute__((weak)) hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s,
                                                           const fx::MaxStar* m, uint32_t* d_ev, uint16_t* d_hist,
-                                                          uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
+                                                          uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters,
+                                                          hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

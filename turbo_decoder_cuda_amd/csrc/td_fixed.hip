@@ -30,6 +30,11 @@
 //                      code instantiated with fx::MaxStar for fx::MaxLog, the table's two words and its shift
 //                      as kernel arguments (scalar registers).  Launched only while a table is set; without
 //                      one a decode launches the kernels above, which do not change.
+//   fx_window_siso_nii_kernel, fx_window_siso_stop_nii_kernel, fx_window_siso_maxstar_nii_kernel,
+//   fx_window_siso_stop_maxstar_nii_kernel  the four sub-block kernels with next-iteration initialisation
+//                      (td_set_fixed_window_nii): the lane code instantiated with NII, the state's two halves
+//                      (read: the previous iteration's, written: this one's) as kernel arguments.  Launched
+//                      only while NII is on; with it off a decode launches the kernels above, which do not change.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
 #include <hip/hip_runtime.h>
 
@@ -192,6 +197,38 @@ __global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_maxstar_kernel(f
     fx::siso_window_stop<DEC>(p, w, s, ev, hist, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
 }
 
+// The four sub-block kernels with next-iteration initialisation (td_set_fixed_window_nii): the same grids, and
+// n, the same in every lane.
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxNii n, int it)
+{
+    fx::siso_window_pass_nii<DEC>(p, w, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
+}
+
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
+                                                                            fx::FxNii n, uint32_t* __restrict__ ev,
+                                                                            uint16_t* __restrict__ hist, int it)
+{
+    fx::siso_window_stop_nii<DEC>(p, w, s, ev, hist, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
+}
+
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_maxstar_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::MaxStar m,
+                                                                               fx::FxNii n, int it)
+{
+    fx::siso_window_pass_nii<DEC>(p, w, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
+}
+
+template <int DEC>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_maxstar_nii_kernel(fx::FxArgs p, fx::FxWindow w,
+                                                                                    fx::FxStop s, fx::MaxStar m, fx::FxNii n,
+                                                                                    uint32_t* __restrict__ ev,
+                                                                                    uint16_t* __restrict__ hist, int it)
+{
+    fx::siso_window_stop_nii<DEC>(p, w, s, ev, hist, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
+}
+
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
 // addition: no atomics, the same bytes on every run.
 template <bool ACC>
@@ -263,12 +300,21 @@ hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, con
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m, uint8_t* d_bits,
-                               hipStream_t st)
+hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m, uint32_t* d_nii,
+                               uint8_t* d_bits, hipStream_t st)
 {
     const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)fx::window_blocks(p.L, w.window));
     for (int it = 0; it < p.iters; ++it) {
-        if (m) {
+        if (d_nii) {
+            const fx::FxNii n0 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 0), n1 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 1);
+            if (m) {
+                hipLaunchKernelGGL(fx_window_siso_maxstar_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, n0, it);
+                hipLaunchKernelGGL(fx_window_siso_maxstar_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, n1, it);
+            } else {
+                hipLaunchKernelGGL(fx_window_siso_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, n0, it);
+                hipLaunchKernelGGL(fx_window_siso_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, n1, it);
+            }
+        } else if (m) {
             hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
             hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
         } else {
@@ -285,7 +331,8 @@ hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const
 }
 
 hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s, const fx::MaxStar* m,
-                                    uint32_t* d_ev, uint16_t* d_hist, uint8_t* d_bits, int32_t* d_iters, hipStream_t st)
+                                    uint32_t* d_ev, uint16_t* d_hist, uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters,
+                                    hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(s.used, 0, p.Bp * sizeof(int32_t), st);   // every codeword runs
     if (e != hipSuccess) return e;
@@ -293,7 +340,16 @@ hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, 
     const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)nS);
     const dim3 jgrid((unsigned)((p.Bp + kTileThreads - 1) / kTileThreads));
     for (int it = 0; it < p.iters; ++it) {
-        if (m) {
+        if (d_nii) {
+            const fx::FxNii n0 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 0), n1 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 1);
+            if (m) {
+                hipLaunchKernelGGL(fx_window_siso_stop_maxstar_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, n0, d_ev, d_hist, it);
+                hipLaunchKernelGGL(fx_window_siso_stop_maxstar_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, n1, d_ev, d_hist, it);
+            } else {
+                hipLaunchKernelGGL(fx_window_siso_stop_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, n0, d_ev, d_hist, it);
+                hipLaunchKernelGGL(fx_window_siso_stop_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, n1, d_ev, d_hist, it);
+            }
+        } else if (m) {
             hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
             hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
         } else {

@@ -325,6 +325,66 @@ TDF_HD void beta_step(int (&bt)[8], int S, int P, const M& mx = M())
     for (int s = 0; s < 8; ++s) bt[s] = n[s];
 }
 
+// Next-iteration initialisation (td_set_fixed_window_nii), next to FxArgs and not in it.  In iterations
+// after the first a warm-up that does not begin at a trellis end starts from the vector that the
+// neighbouring chain had at that position one iteration earlier.  With the overlap a multiple of kW those
+// positions are starts of 16-step windows (or a sub-block's own end), so the stores sit between the
+// windows' step loops and their conditions are the wave's.  A vector is stored relative to its maximum,
+// two int16 a word, in the slot of the sub-block that will start from it: every consumer has one alpha
+// slot and one beta slot per SISO and parity of the iteration.
+//
+// Bounds.  Every stored vector has run at least kW steps from its start, except beta inside the last
+// three positions of the trellis.  Three steps reach every state from every state, so three steps after
+// a vector whose maximum was m every state is at least m - 3 * 509 and at most m + 3 * (509 + 63): the
+// spread of the reachable states is at most 3 * (2 * 509 + 63) = 3243, and the one or two steps next to
+// the termination spread the states they reach by less.  An unreachable state is below kNeg + 2^24,
+// more than 2^27 under the maximum.  So a difference below -32767 means unreachable: it is stored as
+// -32768 and loaded as kNeg, and every other difference fits int16 exactly.  A loaded vector lies in
+// [-3243, 0] (or is kNeg), and from there a recursion runs at most min(3 W + 2 W + 2, L) steps: |metric| <=
+// 3243 + 572 * 10003 < 2^23 and a Lambda term stays below 2^24, the bounds at the head of this file,
+// whatever the number of iterations.
+struct FxNii {
+    const uint32_t* rd;   // [2][nS][4][Bp]: alpha slots, then beta slots, as this SISO left them in iteration it - 1
+    uint32_t* wr;         // the same of this iteration: the other parity, so no launch reads a word that it writes
+    int q, r;             // overlap / window and overlap % window
+};
+
+// words of the NII state: [parity 2][SISO 2][alpha, beta][nS][4][Bp]
+constexpr size_t nii_words(int L, int window, size_t Bp) { return (size_t)32 * window_blocks(L, window) * Bp; }
+
+// the arguments of SISO `dec` in iteration `it` over the state at base
+inline FxNii nii_args(uint32_t* base, int L, const FxWindow& wn, size_t Bp, int it, int dec)
+{
+    const size_t reg = nii_words(L, wn.window, Bp) / 4;
+    return FxNii{base + (size_t)(((it + 1) & 1) * 2 + dec) * reg, base + (size_t)((it & 1) * 2 + dec) * reg,
+                 wn.overlap / wn.window, wn.overlap % wn.window};
+}
+
+TDF_HD void nii_store(uint32_t* slot, size_t Bp, size_t b, const int (&v)[8])
+{
+    int m = v[0];
+#pragma unroll
+    for (int s = 1; s < 8; ++s) m = imax(m, v[s]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int lo = v[2 * j] - m, hi = v[2 * j + 1] - m;
+        lo = lo < -32767 ? -32768 : lo;
+        hi = hi < -32767 ? -32768 : hi;
+        slot[(size_t)j * Bp + b] = ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+    }
+}
+
+TDF_HD void nii_load(const uint32_t* slot, size_t Bp, size_t b, int (&v)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t w = slot[(size_t)j * Bp + b];
+        const int lo = (int16_t)(w & 0xffffu), hi = (int16_t)(w >> 16);
+        v[2 * j] = lo == -32768 ? kNeg : lo;
+        v[2 * j + 1] = hi == -32768 ? kNeg : hi;
+    }
+}
+
 // siso_pass for sub-block sb of the sub-block schedule: positions [sb W, (sb + 1) W), the last
 // sub-block up to L.  alpha warms up from max(sb W - overlap, 0) and beta from min(end + overlap, L);
 // a recursion that starts at the trellis' end starts from the terminated state, any other from equal
@@ -347,9 +407,19 @@ TDF_HD void beta_step(int (&bt)[8], int S, int P, const M& mx = M())
 // previous bits are one 16-bit load together with the window's inputs; the slot is the lane's own, read
 // before it is written.  The codeword's evidence is the fold of its sub-blocks' words, which the launch
 // after SISO2's makes (fx_window_judge_kernel): no atomics, and no launch reads a word of ev that it writes.
-template <int DEC, bool STOP, class M = MaxLog>
+//
+// NII (td_set_fixed_window_nii, ni its state): in iterations after the first a warm-up that does not start at
+// a trellis end loads its start vector from the sub-block's own slot, and the sub-block stores the vectors
+// that others will start from in the next iteration.  With g = q W + r, sub-block sb's chain holds
+//   A[(sb + 1) W - r], the start of sub-block sb + 1 + q: a window start of the forward pass, or for r = 0
+//                      the sub-block's own end, one alpha step past the last window's recompute;
+//   B[sb W + r],       the start of sub-block sb - 1 - q, and in the last sub-block, whose positions run
+//                      past (sb + 1) W, also B[(sb + 1) W + r], the start of sub-block sb - q;
+// bt after the backward loop's window that begins there.  The last sub-block holds no A, as nothing starts
+// to its right.  Every slot that is loaded was stored by the launch of this SISO one iteration earlier.
+template <int DEC, bool STOP, bool NII = false, class M = MaxLog>
 TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop* sp, uint32_t* ev, uint16_t* hist,
-                               size_t b, int it, int sb, const M& mx = M())
+                               const FxNii* ni, size_t b, int it, int sb, const M& mx = M())
 {
     const int L = p.L, K = p.K, W = wn.window;
     const int nS = window_blocks(L, W);
@@ -358,11 +428,21 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
     const bool a_term = start - wn.overlap <= 0, b_term = end + wn.overlap >= L;
     const int a_from = a_term ? 0 : start - wn.overlap, b_from = b_term ? L : end + wn.overlap;
     const int w0 = start / kW, w1 = (end + kW - 1) / kW;   // the sub-block's recomputation windows
+    // NII: the positions whose vectors this sub-block stores (-1: none) and the consumers' slots
+    int a_st = -1, a_slot = 0, b_st0 = -1, b_st1 = -1, b_slot = 0;
+    if (NII && it + 1 < p.iters) {
+        a_slot = sb + 1 + ni->q;
+        if (a_slot <= nS - 1) a_st = start + W - ni->r;
+        b_slot = sb - 1 - ni->q;
+        if (b_slot >= 0) b_st0 = start + ni->r;
+        if (sb == nS - 1 && ni->q >= 1 && b_slot + 1 >= 0 && start + W + ni->r < L) b_st1 = start + W + ni->r;
+    }
 
     {
         int a[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) a[s] = s && a_term ? kNeg : 0;
+        if (NII && it > 0 && !a_term) nii_load(ni->rd + (size_t)sb * 4 * p.Bp, p.Bp, b, a);
         int i = a_from;
         for (; i + kW <= start; i += kW) {
             int S[kW], P[kW];
@@ -386,6 +466,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
         for (int w = w0; w < w1; ++w) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) p.ckpt[((size_t)w * 8 + s) * p.Bp + b] = a[s];
+            if (NII && w * kW == a_st) nii_store(ni->wr + (size_t)a_slot * 4 * p.Bp, p.Bp, b, a);
             if (w == w1 - 1) break;   // a window that is not the sub-block's last is whole
             int S[kW], P[kW];
 #pragma unroll
@@ -403,6 +484,7 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
     int bt[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) bt[s] = s && b_term ? kNeg : 0;
+    if (NII && it > 0 && !b_term) nii_load(ni->rd + (size_t)(nS + sb) * 4 * p.Bp, p.Bp, b, bt);
     {
         int i = b_from;
         for (; i - kW >= end; i -= kW) {
@@ -439,6 +521,11 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
         for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
 #pragma unroll
         for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1], mx);
+        if (NII && a_st == end && w == w1 - 1) {   // the sub-block's own end: its last window is whole
+            int n[8];
+            alpha_step(A[kW - 1], S[kW - 1], P[kW - 1], n, mx);
+            nii_store(ni->wr + (size_t)a_slot * 4 * p.Bp, p.Bp, b, n);
+        }
 #pragma unroll
         for (int t = kW - 1; t >= 0; --t) {
             const int i = i0 + t;
@@ -481,6 +568,8 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
             if (it + 2 >= sp->first && it + 1 < p.iters)   // there is a next iteration, and it is judged
                 hist[(size_t)w * p.Bp + b] = (uint16_t)now;
         }
+        if (NII && (i0 == b_st0 || i0 == b_st1))
+            nii_store(ni->wr + (size_t)(nS + (i0 == b_st0 ? b_slot : b_slot + 1)) * 4 * p.Bp, p.Bp, b, bt);
     }
     if (STOP && judge) ev[(size_t)sb * p.Bp + b] = (uint32_t)acc;
 }
@@ -488,7 +577,14 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
 template <int DEC, class M = MaxLog>
 TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb, const M& mx = M())
 {
-    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, b, it, sb, mx);
+    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, nullptr, b, it, sb, mx);
+}
+
+template <int DEC, class M = MaxLog>
+TDF_HD void siso_window_pass_nii(const FxArgs& p, const FxWindow& wn, const FxNii& ni, size_t b, int it, int sb,
+                                 const M& mx = M())
+{
+    siso_window_pass_t<DEC, false, true>(p, wn, nullptr, nullptr, nullptr, &ni, b, it, sb, mx);
 }
 
 // true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
@@ -537,7 +633,17 @@ TDF_HD void siso_window_stop(const FxArgs& p, const FxWindow& wn, const FxStop& 
 {
     const bool run = b < (size_t)p.B && s.used[b] == 0;
     if (!any_lane(run)) return;
-    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, b, it, sb, mx);
+    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, nullptr, b, it, sb, mx);
+}
+
+// The same with NII: a codeword that runs in iteration `it` ran in it - 1, so its slots hold its own vectors.
+template <int DEC, class M = MaxLog>
+TDF_HD void siso_window_stop_nii(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist,
+                                 const FxNii& ni, size_t b, int it, int sb, const M& mx = M())
+{
+    const bool run = b < (size_t)p.B && s.used[b] == 0;
+    if (!any_lane(run)) return;
+    if (run) siso_window_pass_t<DEC, true, true>(p, wn, &s, ev, hist, &ni, b, it, sb, mx);
 }
 
 // The decision after SISO2's launch of iteration `it`, one call per codeword: a running codeword stops

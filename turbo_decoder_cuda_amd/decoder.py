@@ -62,6 +62,7 @@ class TurboCodec:
         self.device = int(device)
         self.early_stop = None   # set_early_stop / set_window_early_stop / set_fixed_early_stop
         self._window_stop = False   # the rule in self.early_stop is the windowed schedule's
+        self._fixed_window, self._fixed_nii = (0, 0), False   # set_fixed_window's last setting
 
     # -- lifetime (TurboCodingRelease) -------------------------------------------------
     def close(self) -> None:
@@ -123,16 +124,39 @@ class TurboCodec:
         f = N.TdFixedParams(int(le_max), int(ext_scale_q))
         N.check(N.lib().td_set_fixed(self._h, C.byref(f)))
 
-    def set_fixed_window(self, window: int = 64, overlap: int = 48) -> None:
+    def set_fixed_window(self, window: int = 64, overlap: int = 48, nii: bool = False) -> None:
         """The fixed-point decoder's sub-block schedule (td_set_fixed_window; precision="fixed" only):
         sub-blocks of `window` positions (a multiple of 16) that warm up over `overlap` positions on each
         side and run in parallel, for batches that do not fill the chip with a lane per codeword.
         window=0: the exact schedule.  Excludes set_fixed_early_stop (its rule is
         set_fixed_window_early_stop's).  The default overlap is the smallest
         measured one whose bit and frame errors stay within 1.1x the exact schedule's at 0.4, 0.5 and
-        0.6 dB (K = 6144; DESIGN.md "Fixed point", profiles/fixed/window_ber.json)."""
-        w = N.TdFixedWindowParams(int(window), int(overlap))
-        N.check(N.lib().td_set_fixed_window(self._h, C.byref(w)))
+        0.6 dB (K = 6144; DESIGN.md "Fixed point", profiles/fixed/window_ber.json).
+        nii: next-iteration initialisation (td_set_fixed_window_nii): from the second iteration on a
+        warm-up starts from the metrics the neighbouring sub-block had there one iteration earlier, which
+        lets a smaller overlap do; the overlap must then be a multiple of 16.  Window, overlap and nii are
+        set together: on an error the call raises and the handle keeps its previous three.  Call reserve()
+        after it: the NII state is part of the workspace only while nii is on."""
+        L, new = N.lib(), (int(window), int(overlap))
+        on = bool(nii) and new[0] != 0
+        prev, prev_on = self._fixed_window, self._fixed_nii
+
+        def put(win, flag):
+            N.check(L.td_set_fixed_window(self._h, C.byref(N.TdFixedWindowParams(*win))))
+            if flag:
+                N.check(L.td_set_fixed_window_nii(self._h, 1))
+
+        try:
+            if prev_on and not on:   # off first: the new overlap is then free
+                N.check(L.td_set_fixed_window_nii(self._h, 0))
+            put(new, on)
+        except N.TurboError:
+            try:   # back to the previous three (a failed C call changed nothing, an earlier one of this call did)
+                put(prev, prev_on)
+            except N.TurboError:
+                pass
+            raise
+        self._fixed_window, self._fixed_nii = new if new[0] else (0, 0), on
         if not int(window) and self._window_stop:   # td_set_fixed_window(0) clears the sub-block schedule's rule
             self.early_stop, self._window_stop = None, False
 
