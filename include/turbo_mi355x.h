@@ -474,6 +474,19 @@ int td_debug_placement(td_handle* h, float* ms, int cap, int* pick);
 int td_debug_placement_cost(td_handle* h, double* wall_ms, double* held_bytes);
 /* Bytes of the handle's decode workspace (0 before the first reserve / decode). */
 int td_debug_workspace_bytes(td_handle* h, unsigned long long* bytes);
+/* Fill the handle's scratch with one byte, so that a test can show that no decode depends on what its
+ * workspace held before (tests only).  byte in 0..255: synchronises the device, sets every device
+ * buffer a decode uses as scratch to that byte -- the decode workspace, the windowed schedule's buffers
+ * (second extrinsic pair, checkpoints, NII metrics, bits, stop state) and td_decode_host's staging
+ * buffers, where allocated -- synchronises again and arms the handle: from then on every allocation or
+ * growth of those buffers (td_reserve's kept candidate included) and td_siso_host's scratch are filled
+ * with the same byte right after they are allocated.  byte == -1 disarms the handle.  The handle's
+ * tables (permutations, max* tables, lane tables, CU slots, CRC syndromes, rate-matching tables) and
+ * the frame generator's state are never touched.  *filled (may be null) receives the bytes this call
+ * wrote.  Must not be called while a stream is capturing (it synchronises the device), and an armed
+ * handle must not allocate inside a capture either (td_reserve first, as always).  A disarmed handle
+ * launches and synchronises exactly what it did without this call.  TD_EINVAL for any other byte. */
+int td_debug_workspace_fill(td_handle* h, int byte, unsigned long long* filled);
 /* The placement search's stop rule on probe times ms[0..n) (host only, for tests): 1 if the search
  * would stop after them (the fast mode seen), else 0; TD_EINVAL on a bad argument. */
 int td_debug_placement_rule(const float* ms, int n);

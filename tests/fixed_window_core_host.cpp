@@ -37,7 +37,7 @@ int main(int argc, char** argv)
     const size_t Bp = (size_t)B + 1;   // an odd pitch: one lane of padding, as the kernel's last wave has
     std::vector<int8_t> xs((size_t)(L + 3) * Bp, 0), xp1((size_t)L * Bp, 0), xp2((size_t)L * Bp, 0);
     std::vector<int16_t> e12((size_t)K * Bp, 0x5a5a), e21((size_t)K * Bp, 0x5a5a);
-    std::vector<int32_t> ck((size_t)nW * 8 * Bp);
+    std::vector<int32_t> ck((size_t)nW * 8 * Bp, 0x5a5a5a5a);   // read before written: wrong bits, or a signed overflow under UBSan
     std::vector<uint8_t> bT((size_t)rows * K * Bp, 9);
     std::vector<int16_t> le((size_t)B * iters * 2 * L, 0x5a5a);
     auto c = [](int8_t v) { return v == -128 ? (int8_t)-127 : v; };

@@ -86,6 +86,7 @@ int main()
     CHECK(td_set_window_maxstar(nullptr, TD_WMAXSTAR_FAST) == TD_EINVAL);
     CHECK(td_debug_window_layout(nullptr, 0, 0, 0) == TD_EINVAL);
     CHECK(td_debug_workspace_bytes(nullptr, nullptr) == TD_EINVAL);
+    CHECK(td_debug_workspace_fill(nullptr, 0, nullptr) == TD_EINVAL);
     CHECK(td_profile_enable(nullptr, 1) == TD_EINVAL);
     CHECK(td_synth_seed(nullptr, 1) == TD_EINVAL);
     CHECK(td_modulate(nullptr, 1, 1, nullptr, nullptr, nullptr) == TD_EINVAL);

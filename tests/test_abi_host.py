@@ -165,6 +165,7 @@ def test_null_handle_calls_are_errors():
     assert L.td_set_window_maxstar(None, 0) == N.TD_EINVAL
     assert L.td_debug_window_layout(None, 0, 0, 0) == N.TD_EINVAL
     assert L.td_debug_workspace_bytes(None, None) == N.TD_EINVAL
+    assert L.td_debug_workspace_fill(None, 0, None) == N.TD_EINVAL
 
 
 def test_window_steps_is_the_kernel_window():

@@ -31,7 +31,7 @@ EXPORTS = (
     "td_decode_host_stop", "td_crc24_host", "td_crc24_syndromes", "td_set_window_stop",
     "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
     "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window", "td_set_fixed_window_stop",
-    "td_set_fixed_maxstar", "td_fixed_maxstar_table", "td_set_fixed_window_nii",
+    "td_set_fixed_maxstar", "td_fixed_maxstar_table", "td_set_fixed_window_nii", "td_debug_workspace_fill",
 )
 
 
@@ -145,6 +145,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "td_set_fixed_maxstar"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_set_fixed_maxstar.argtypes = [P, C.POINTER(TdFixedMaxstarParams)]
         L.td_fixed_maxstar_table.argtypes = [C.c_double, I, C.POINTER(TdFixedMaxstarParams)]
+    if hasattr(L, "td_debug_workspace_fill"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_debug_workspace_fill.argtypes = [P, I, C.POINTER(C.c_ulonglong)]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

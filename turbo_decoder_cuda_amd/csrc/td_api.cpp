@@ -140,6 +140,8 @@ struct td_handle {
     // next-iteration initialisation of the sub-block schedule (td_set_fixed_window_nii): its state follows the
     // workspace's carve while it is on
     bool fnii = false;
+    // td_debug_workspace_fill: the byte every fresh scratch allocation is filled with; -1 = disarmed
+    int poison = -1;
 };
 
 namespace td {
@@ -246,6 +248,16 @@ Carve carve_for(const td_handle* h, int G) { return carve(G, h->p.K, h->elem, h-
 hipError_t ws_malloc(void** p, size_t size) { return hipMalloc(p, size); }
 hipError_t ws_release(void* p) { return hipFree(p); }
 
+// td_debug_workspace_fill, armed: a scratch buffer that was just allocated gets the handle's byte before
+// anything is enqueued on it (the device is idle after the call: the caller's streams need not be the null
+// stream).  Disarmed: nothing, one compare.
+hipError_t poison_fresh(const td_handle* h, void* p, size_t size)
+{
+    if (h->poison < 0 || !p || !size) return hipSuccess;
+    const hipError_t e = hipMemset(p, h->poison, size);
+    return e != hipSuccess ? e : hipDeviceSynchronize();
+}
+
 // the workspace for G groups in the handle's current layout (grown, never shrunk)
 int ensure_ws(td_handle* h, int G)
 {
@@ -262,6 +274,7 @@ int ensure_ws(td_handle* h, int G)
         return fail(TD_ENOMEM, "hipMalloc of the decode workspace failed (" + std::to_string(c.total) + " B)");
     }
     h->ws_bytes = c.total;
+    TD_HIP(poison_fresh(h, h->d_ws, h->ws_bytes));
     return TD_OK;
 }
 
@@ -455,6 +468,7 @@ int place_ws(td_handle* h, int G)
     h->d_ws = s.cand[best].second;
     s.cand[best].second = nullptr;   // kept; the guard frees the others and the spacers
     h->ws_bytes = c.total;
+    TD_HIP(poison_fresh(h, h->d_ws, h->ws_bytes));
     return TD_OK;
 }
 
@@ -497,6 +511,7 @@ int ensure_wws(td_handle* h, size_t need)
             return fail(TD_ENOMEM, "hipMalloc of the windowed-schedule buffers failed (" + std::to_string(need) + " B)");
         }
         h->wws_bytes = need;
+        TD_HIP(poison_fresh(h, h->d_wws, need));
     }
     return TD_OK;
 }
@@ -674,6 +689,7 @@ int ensure_fixed_ws(td_handle* h, int B)
         return fail(TD_ENOMEM, "hipMalloc of the decode workspace failed (" + std::to_string(c.total) + " B)");
     }
     h->ws_bytes = c.total;
+    TD_HIP(poison_fresh(h, h->d_ws, h->ws_bytes));
     return TD_OK;
 }
 
@@ -793,6 +809,10 @@ int siso_host_t(td_handle* h, const void* recs, const void* La, int terminated, 
     const size_t total = 5 * align_up(eL, 256) + align_up(eA, 256) + align_up(inR, 256) + 2 * align_up(inA, 256) +
                          align_up(eP, 256);
     if (hipMalloc(&buf, total) != hipSuccess) return fail(TD_ENOMEM, "hipMalloc (siso) failed");
+    if (poison_fresh(h, buf, total) != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(TD_EHIP, "td_siso_host: the debug fill of its scratch failed");
+    }
     size_t o = 0;
     auto take = [&](size_t n) {
         char* p = buf + o;
@@ -1474,6 +1494,35 @@ int td_debug_workspace_bytes(td_handle* h, unsigned long long* bytes)
     return TD_OK;
 }
 
+int td_debug_workspace_fill(td_handle* h, int byte, unsigned long long* filled)
+{
+    if (!h) return fail(TD_EINVAL, "td_debug_workspace_fill: null handle");
+    if (byte < -1 || byte > 255) return fail(TD_EINVAL, "td_debug_workspace_fill: byte must be -1 or in [0, 255]");
+    if (filled) *filled = 0;
+    if (byte < 0) {
+        h->poison = -1;
+        return TD_OK;
+    }
+    TD_HIP(hipSetDevice(h->p.device));
+    TD_HIP(hipDeviceSynchronize());   // no decode still runs on what is about to be overwritten
+    // the scratch only: the tables (d_pi, d_pinv, d_lut, d_qlut, d_lane, d_slots, d_crc, d_rm_*) and the
+    // generator's d_win hold what later launches read as it is
+    const std::pair<void*, size_t> bufs[] = {
+        {h->d_ws, h->ws_bytes},    {h->d_wws, h->wws_bytes},          {h->d_hin, h->hin_b},
+        {h->d_hbits, h->hbits_b},  {h->d_hle, h->hle_b},              {h->d_hiters, h->hiters_b},
+    };
+    unsigned long long n = 0;
+    for (const auto& b : bufs) {
+        if (!b.first || !b.second) continue;
+        TD_HIP(hipMemset(b.first, byte, b.second));
+        n += b.second;
+    }
+    TD_HIP(hipDeviceSynchronize());
+    h->poison = byte;
+    if (filled) *filled = n;
+    return TD_OK;
+}
+
 int td_debug_placement_rule(const float* ms, int n)
 {
     if (!ms || n < 0) return fail(TD_EINVAL, "td_debug_placement_rule: bad argument");
@@ -1506,14 +1555,15 @@ int td_decode_host_stop(td_handle* h, const void* llr, int B, int* out, void* le
     const size_t bits_b = (size_t)B * it * K;
     const size_t le_b = le ? (size_t)B * it * 2 * L * (is_fixed(h) ? sizeof(int16_t) : h->elem) : 0;
     // staging buffers kept by the handle (grown on demand), so a warm per-frame caller allocates nothing
-    auto grow = [](void** p, size_t& cap, size_t need) {
+    auto grow = [h](void** p, size_t& cap, size_t need) {
         if (need <= cap) return hipSuccess;
         if (*p) (void)hipFree(*p);
         *p = nullptr;
         cap = 0;
         const hipError_t e = hipMalloc(p, need);
-        if (e == hipSuccess) cap = need;
-        return e;
+        if (e != hipSuccess) return e;
+        cap = need;
+        return poison_fresh(h, *p, need);
     };
     if (grow(&h->d_hin, h->hin_b, in_b) != hipSuccess || grow(reinterpret_cast<void**>(&h->d_hbits), h->hbits_b, bits_b) != hipSuccess ||
         (le && grow(&h->d_hle, h->hle_b, le_b) != hipSuccess) ||

@@ -110,6 +110,14 @@ class TurboCodec:
         N.check(N.lib().td_debug_workspace_bytes(self._h, C.byref(v)))
         return int(v.value)
 
+    def debug_fill_workspace(self, byte: int) -> int:
+        """Fill every scratch buffer of the handle with `byte` (0..255) and arm it: later allocations of
+        scratch get the same byte (td_debug_workspace_fill; tests).  byte=-1 disarms.  Returns the bytes
+        this call wrote.  Synchronises the device: never inside a stream capture."""
+        v = C.c_ulonglong(0)
+        N.check(N.lib().td_debug_workspace_fill(self._h, int(byte), C.byref(v)))
+        return int(v.value)
+
     def _torch_dtypes(self):
         """(LLR dtype, Le dtype) of the device-resident calls."""
         import torch
