@@ -584,6 +584,39 @@ int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d
 /* Host only (no GPU, no handle): idx[k] = the stream position of e_k, k < E.  1 <= K <= 10000. */
 int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx);
 
+/*
+ * The transmit side on device-resident bits (an extension: the reference encodes one frame per call on the
+ * host, TurboEnCoding, log_map.cpp:530-583, which the compat layer keeps).  With these the chain closes on
+ * the GPU: td_crc_attach -> td_encode_device -> td_rate_match -> td_modulate -> (the caller's channel) ->
+ * td_demodulate -> td_rate_dematch -> td_decode_device.  They work on a handle of any precision and use
+ * only its K, f1, f2, device and QPP table.
+ *
+ * td_encode_device: d_info [B][K] uint8 (any non-zero byte is a 1, as td_crc24_host reads them) ->
+ * d_coded [B][3K+12] uint8, each 0 or 1, in the stream layout of encoderm_turbo (log_map.cpp:566-578):
+ * (x, p1, p2) per info bit, then the first encoder's three tail (x, p) pairs, then the second encoder's.
+ * It is the layout td_rate_match (elem_size 1) and td_modulate take.  Both constituent encoders are the
+ * RSC 13/15 of encode_bit (log_map.cpp:247-269), zero start, trellis-terminated; the second one reads
+ * u[pi(i)].  Asynchronous on `stream`, allocates nothing, may be captured into a hipGraph.  Pointers need
+ * only byte alignment; the bytes do not depend on it.  B = 0 is a no-op.  Any K the handle allows
+ * (1 .. 10000).  TD_EINVAL: a null handle or pointer, B < 0.
+ */
+int td_encode_device(td_handle* h, const uint8_t* d_info, int B, uint8_t* d_coded, void* stream);
+/* Builds and uploads the per-position syndrome table (td_crc24_syndromes) for (K, poly): poly = the
+ * generator's 24 low-order coefficients, 0x800063 gCRC24B, 0x864CFB gCRC24A (td_stop_params.crc_poly's
+ * convention).  Like td_rm_set it may synchronise and allocate.  It may be called again with another poly.
+ * The table is independent of the stop rules' (td_set_early_stop and its siblings): setting or clearing a
+ * rule does not disturb it, nor the reverse.  A failed call leaves the previous table in place.
+ * TD_EINVAL: a null handle, poly == 0, coefficients above the 24 low-order ones, K <= 24. */
+int td_crc_set(td_handle* h, uint32_t poly);
+/* In place: bits K-24 .. K-1 of every row of d_bits [B][K] become the CRC-24 of bits 0 .. K-25 (most
+ * significant remainder bit first, each byte 0 or 1), whatever they held; bits 0 .. K-25 are only read.
+ * Afterwards td_crc24_host(row, K, poly) == 0.  Asynchronous on `stream`, allocates nothing, may be
+ * captured.  B = 0 is a no-op.  TD_EINVAL: a null handle or pointer, B < 0, a call before td_crc_set. */
+int td_crc_attach(td_handle* h, uint8_t* d_bits, int B, void* stream);
+/* d_rem[b] = td_crc24_host(row b of d_bits [B][K], K, poly): 0 = the block passes.  Launch and argument
+ * rules as td_crc_attach. */
+int td_crc_check(td_handle* h, const uint8_t* d_bits, int B, uint32_t* d_rem, void* stream);
+
 /* Last error message of this thread ("" if none). */
 const char* td_last_error(void);
 /* Number of visible HIP devices (0 on a host without a GPU; never fails). */

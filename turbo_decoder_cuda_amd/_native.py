@@ -32,6 +32,7 @@ EXPORTS = (
     "td_rm_set", "td_rm_info", "td_rate_match", "td_rate_dematch", "td_rm_index_host",
     "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window", "td_set_fixed_window_stop",
     "td_set_fixed_maxstar", "td_fixed_maxstar_table", "td_set_fixed_window_nii", "td_debug_workspace_fill",
+    "td_encode_device", "td_crc_set", "td_crc_attach", "td_crc_check",
 )
 
 
@@ -147,6 +148,11 @@ def lib() -> C.CDLL:
         L.td_fixed_maxstar_table.argtypes = [C.c_double, I, C.POINTER(TdFixedMaxstarParams)]
     if hasattr(L, "td_debug_workspace_fill"):   # (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_debug_workspace_fill.argtypes = [P, I, C.POINTER(C.c_ulonglong)]
+    if hasattr(L, "td_encode_device"):   # the transmit side (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_encode_device.argtypes = [P, P, I, P, P]
+        L.td_crc_set.argtypes = [P, C.c_uint32]
+        L.td_crc_attach.argtypes = [P, P, I, P]
+        L.td_crc_check.argtypes = [P, P, I, P, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "td_crc.h"
+#include "td_encode.h"
 #include "td_fixed.h"
 #include "td_kernels.h"
 #include "td_ratematch.h"
@@ -125,6 +126,10 @@ struct td_handle {
     int32_t* d_rm_rank = nullptr;
     int32_t* d_rm_pos = nullptr;
     bool rm_set = false;
+    // CRC attach / check (td_crc_set): [K] syndromes by natural bit position, a table of its own -- the stop
+    // rules' d_crc is theirs (a fixed handle's is in interleaved order), so neither setter disturbs the other
+    uint32_t* d_crc_tab = nullptr;
+    uint32_t crc_tab_poly = 0;   // 0 = td_crc_set not called yet
     // the fixed-point decoder (TD_FIXED): the extrinsic's clamp and scale (td_set_fixed)
     td_fixed_params fxp{255, 3};
     // the fixed-point decoder's correction table (td_set_fixed_maxstar): off = Max-Log-MAP
@@ -1087,6 +1092,7 @@ int td_destroy(td_handle* h)
     if (h->d_wws) (void)hipFree(h->d_wws);
     if (h->d_rm_rank) (void)hipFree(h->d_rm_rank);
     if (h->d_rm_pos) (void)hipFree(h->d_rm_pos);
+    if (h->d_crc_tab) (void)hipFree(h->d_crc_tab);
     release_wstr(h->wstr);
     for (auto& tri : h->ev)
         for (auto& e : tri) (void)hipEventDestroy(e);
@@ -1797,6 +1803,77 @@ int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx)
         idx[k] = t.pos[j];
         if (++j == (size_t)t.Nnn) j = 0;
     }
+    return TD_OK;
+}
+
+
+int td_encode_device(td_handle* h, const uint8_t* d_info, int B, uint8_t* d_coded, void* stream)
+{
+    if (!h) return fail(TD_EINVAL, "td_encode_device: null handle");
+    if (!d_info || !d_coded) return fail(TD_EINVAL, "td_encode_device: null pointer");
+    if (B < 0) return fail(TD_EINVAL, "td_encode_device: negative B");
+    if (B == 0) return TD_OK;
+    if (!td::launch_encode) return fail(TD_EHIP, "td_encode_device: this build has no td_encode.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    const td::EncParams p{h->p.K, B, h->d_pi, d_info, d_coded, h->role_cus};
+    TD_HIP(td::launch_encode(p, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_crc_set(td_handle* h, uint32_t poly)
+{
+    if (!h) return fail(TD_EINVAL, "td_crc_set: null handle");
+    if (poly == 0 || (poly & ~td::kCrc24Mask))
+        return fail(TD_EINVAL, "td_crc_set: poly must be the 24 low-order coefficients, non-zero");
+    if (h->p.K <= 24) return fail(TD_EINVAL, "td_crc_set: a CRC-24 needs K > 24");
+    TD_HIP(hipSetDevice(h->p.device));
+    if (!h->d_crc_tab && hipMalloc(reinterpret_cast<void**>(&h->d_crc_tab), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
+        h->d_crc_tab = nullptr;
+        return fail(TD_ENOMEM, "td_crc_set: hipMalloc failed");
+    }
+    std::vector<uint32_t> tab((size_t)h->p.K);
+    td::crc24_syndromes(h->p.K, poly, tab.data());
+    TD_HIP(hipDeviceSynchronize());   // launches that still read the previous table
+    TD_HIP(hipMemcpy(h->d_crc_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->crc_tab_poly = poly;
+    return TD_OK;
+}
+
+namespace {
+
+// the argument checks td_crc_attach and td_crc_check share
+int crc_launch_params(const char* who, td_handle* h, const void* a, const void* b, int B, td::CrcParams& p)
+{
+    const std::string w(who);
+    if (!h) return fail(TD_EINVAL, w + ": null handle");
+    if (!a || !b) return fail(TD_EINVAL, w + ": null pointer");
+    if (B < 0) return fail(TD_EINVAL, w + ": negative B");
+    if (!h->crc_tab_poly) return fail(TD_EINVAL, w + ": call td_crc_set first");
+    p = td::CrcParams{h->p.K, B, h->d_crc_tab, h->role_cus};
+    return TD_OK;
+}
+
+}  // namespace
+
+int td_crc_attach(td_handle* h, uint8_t* d_bits, int B, void* stream)
+{
+    td::CrcParams p;
+    if (const int rc = crc_launch_params("td_crc_attach", h, d_bits, d_bits, B, p)) return rc;
+    if (B == 0) return TD_OK;
+    if (!td::launch_crc_attach) return fail(TD_EHIP, "td_crc_attach: this build has no td_encode.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    TD_HIP(td::launch_crc_attach(p, d_bits, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_crc_check(td_handle* h, const uint8_t* d_bits, int B, uint32_t* d_rem, void* stream)
+{
+    td::CrcParams p;
+    if (const int rc = crc_launch_params("td_crc_check", h, d_bits, d_rem, B, p)) return rc;
+    if (B == 0) return TD_OK;
+    if (!td::launch_crc_check) return fail(TD_EHIP, "td_crc_check: this build has no td_encode.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    TD_HIP(td::launch_crc_check(p, d_bits, d_rem, static_cast<hipStream_t>(stream)));
     return TD_OK;
 }
 

@@ -413,6 +413,63 @@ class TurboCodec:
                                         int(bool(accumulate)), C.c_void_p(stream.cuda_stream)))
         return out
 
+    # -- the transmit side: CRC-24 attach / check and the encoder (td_crc_set / td_crc_attach /
+    #    td_crc_check / td_encode_device) ----------------------------------------------------
+    def encode(self, info, out=None, stream=None):
+        """info: uint8 tensor [B, K] on this codec's device (any non-zero byte is a 1) -> the coded stream
+        uint8 [B, 3K+12] of encoderm_turbo, each byte 0 or 1: what rate_match and modulate take."""
+        import torch
+
+        self._check_in("info", info, (torch.uint8,), self.K)
+        B = info.shape[0]
+        if out is None:
+            out = torch.empty((B, stream_length(self.K)), dtype=torch.uint8, device=info.device)
+        else:
+            self._check_out("out", out, torch.uint8, (B, stream_length(self.K)), info.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(info.device)
+        if B:   # (an empty tensor has no address to pass)
+            N.check(N.lib().td_encode_device(self._h, C.c_void_p(info.data_ptr()), B, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(stream.cuda_stream)))
+        return out
+
+    def set_crc(self, poly: int = N.CRC24B) -> None:
+        """The CRC-24 generator of crc_attach / crc_check (td_crc_set): its 24 low-order coefficients,
+        gCRC24B by default.  Needs K > 24.  Independent of the early-termination rules' polynomial."""
+        N.check(N.lib().td_crc_set(self._h, int(poly) & 0xFFFFFFFF))
+        self.crc_poly = int(poly)
+
+    def crc_attach(self, bits, stream=None):
+        """bits: uint8 tensor [B, K] on this codec's device.  In place: the last 24 bytes of every row
+        become the CRC-24 of the K-24 before them (most significant bit first).  Returns bits.  After set_crc."""
+        import torch
+
+        self._check_in("bits", bits, (torch.uint8,), self.K)
+        if stream is None:
+            stream = torch.cuda.current_stream(bits.device)
+        if bits.shape[0]:
+            N.check(N.lib().td_crc_attach(self._h, C.c_void_p(bits.data_ptr()), bits.shape[0],
+                                          C.c_void_p(stream.cuda_stream)))
+        return bits
+
+    def crc_check(self, bits, out=None, stream=None):
+        """bits: uint8 tensor [B, K] -> the CRC-24 remainder of every row, a [B] tensor of 32-bit values
+        (0 = the block passes; td_crc24_host of the row).  After set_crc."""
+        import torch
+
+        self._check_in("bits", bits, (torch.uint8,), self.K)
+        B = bits.shape[0]
+        if out is None:
+            out = torch.empty((B,), dtype=torch.int32, device=bits.device)
+        else:
+            self._check_out("out", out, torch.int32, (B,), bits.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(bits.device)
+        if B:
+            N.check(N.lib().td_crc_check(self._h, C.c_void_p(bits.data_ptr()), B, C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(stream.cuda_stream)))
+        return out
+
     # -- measurement ---------------------------------------------------------------------
     def profile(self, on: bool = True) -> None:
         """Bracket the next decodes' kernels with hipEvents (see td_profile_enable)."""
