@@ -8,6 +8,7 @@ import pytest
 import fixed_ref as F
 import fixed_size_cases as Z
 import pyoracle as O
+from fixed_host import core_host, run_core   # noqa: F401  (core_host is a fixture)
 from turbo_decoder_cuda_amd import _native as N
 
 CODES = [(8, 3, 4), (40, 3, 10), (1024, 31, 64), (6144, 263, 480)]
@@ -85,38 +86,10 @@ def test_saturating_dematch_reference():
 
 
 # ------------------------------------------------------------------ the kernel's arithmetic on the host
-SAN = ["-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"]
-
-
-@pytest.fixture(scope="module")
-def core_host(tmp_path_factory):
-    """tests/fixed_core_host.cpp: csrc/td_fixed_core.h (what a lane of the gfx950 kernel runs) as a
-    stand-alone host program under ASan + UBSan."""
-    import os
-    import subprocess
-    from conftest import REPO
-    exe = str(tmp_path_factory.mktemp("fixed_core") / "fixed_core_host")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", *SAN, f"-I{REPO}/turbo_decoder_cuda_amd/csrc",
-                           os.path.join(REPO, "tests", "fixed_core_host.cpp"), "-o", exe])
-    return exe
-
-
 def _run_core(exe, tmp_path, q, K, f1, f2, iters, all_iters, le_max, scale):
-    import os
-    import subprocess
-    B, L = q.shape[0], K + 3
-    rows = iters if all_iters else 1
-    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(fin, "wb") as f:
-        f.write(np.array([K, iters, int(all_iters), le_max, scale, B], dtype=np.int32).tobytes())
-        f.write(O.qpp(K, f1, f2).astype(np.int32).tobytes())
-        f.write(np.ascontiguousarray(q).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    raw = np.fromfile(fout, dtype=np.uint8)
-    nb = B * rows * K
-    return raw[:nb].reshape(B, rows, K), raw[nb:].view(np.int16).reshape(B, iters, 2, L)
+    """tests/fixed_core_host.cpp (csrc/td_fixed_core.h, what a lane of the gfx950 kernel runs, as a stand-alone
+    host program under ASan + UBSan): the exact schedule, no rule, no table."""
+    return run_core(exe, tmp_path, q, O.qpp(K, f1, f2), iters, all_iters, (le_max, scale))[:2]
 
 
 @pytest.mark.parametrize("K,f1,f2,iters,setting", [(8, 3, 4, 3, (255, 4)), (13, 1, 0, 2, (31, 2)), (16, 1, 4, 2, (255, 3)),

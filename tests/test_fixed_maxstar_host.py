@@ -8,8 +8,6 @@ The setter's checks that need a handle (another precision, shift, entries, corr[
 test_gpu_fixed_maxstar.py: td_create needs a device."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +18,7 @@ import fixed_size_cases as Z
 import fixed_stop_cases as S
 import pyoracle as O
 import window_stop_cases as W
+from fixed_host import SENTINEL, core_host, run_core   # noqa: F401  (core_host is a fixture)
 from turbo_decoder_cuda_amd import _native as N
 
 
@@ -111,38 +110,9 @@ def test_fewer_bit_errors_than_maxlog():
 
 
 # ------------------------------------------------------------------ the kernels' lane code on the host
-SAN = ["-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"]
-SENTINEL = 0x5a5a
-RULES = {None: 0, "hda": 1, "crc": 2}
-
-
-@pytest.fixture(scope="module")
-def core_host(tmp_path_factory):
-    from conftest import REPO
-    exe = str(tmp_path_factory.mktemp("fixed_maxstar_core") / "fixed_maxstar_core_host")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", *SAN, f"-I{REPO}/turbo_decoder_cuda_amd/csrc",
-                           os.path.join(REPO, "tests", "fixed_maxstar_core_host.cpp"), "-o", exe])
-    return exe
-
-
 def _run_core(exe, tmp_path, q, K, iters, all_iters, setting, win, rule, min_iters, tab):
-    B, L = q.shape[0], K + 3
-    rows = iters if all_iters else 1
-    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(fin, "wb") as f:
-        f.write(np.array([K, iters, int(all_iters), *setting, B, *(win or (0, 0)), RULES[rule], min_iters, S.CRC24B,
-                          0 if tab is None else 1, *((0,) + (0,) * 8 if tab is None else (tab[0], *tab[1]))],
-                         dtype=np.int32).tobytes())
-        f.write(O.qpp(K, *S.QPP[K]).astype(np.int32).tobytes())
-        f.write(np.ascontiguousarray(q).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, \
-        (r.returncode, r.stderr[-3000:])
-    raw = np.fromfile(fout, dtype=np.uint8)
-    nb, nl = B * rows * K, B * iters * 2 * L * 2
-    return (raw[:nb].reshape(B, rows, K), raw[nb:nb + nl].view(np.int16).reshape(B, iters, 2, L),
-            raw[nb + nl:].view(np.int32))
+    return run_core(exe, tmp_path, q, O.qpp(K, *S.QPP[K]), iters, all_iters, setting, win, rule, min_iters, S.CRC24B, tab,
+                    timeout=600)
 
 
 @functools.lru_cache(maxsize=None)

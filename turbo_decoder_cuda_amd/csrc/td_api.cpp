@@ -702,8 +702,7 @@ int ensure_fixed_ws(td_handle* h, int B)
 int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int all_iters, void* d_le, int32_t* d_iters,
                  hipStream_t st)
 {
-    if (!td::launch_fixed_demux || !td::launch_fixed_turbo || !td::launch_fixed_turbo_stop || !td::launch_fixed_window ||
-        !td::launch_fixed_window_stop)
+    if (!td::launch_fixed_demux || !td::launch_fixed_decode)
         return fail(TD_EHIP, "td_decode_device: this build has no td_fixed.hip");
     int rc = ensure_fixed_ws(h, B);
     if (rc) return rc;
@@ -759,32 +758,20 @@ int decode_fixed(td_handle* h, const void* d_llr, int B, uint8_t* d_bits, int al
     hipError_t e = td::launch_fixed_demux(a, static_cast<const int8_t*>(d_llr), st);
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_demux");
     if (ev) TD_HIP(hipEventRecord(ev[1], st));
-    if (h->fstop.rule != TD_STOP_NONE) {
-        const bool hda = h->fstop.rule == TD_STOP_HDA;
-        td::fx::FxStop s{};
-        s.rule = h->fstop.rule;
-        s.first = std::max(hda ? 2 : 1, h->fstop.min_iters);
-        s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
-        s.used = reinterpret_cast<int32_t*>(ws + c.used);
-        e = td::launch_fixed_turbo_stop(a, s, m, d_bits, d_iters, st);
-    } else if (h->fwin.window && h->fwstop.rule != TD_STOP_NONE) {
-        const bool hda = h->fwstop.rule == TD_STOP_HDA;
-        td::fx::FxStop s{};
-        s.rule = h->fwstop.rule;
-        s.first = std::max(hda ? 2 : 1, h->fwstop.min_iters);
-        s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
-        s.used = reinterpret_cast<int32_t*>(ws + c.used);
-        e = td::launch_fixed_window_stop(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, s, m,
-                                         reinterpret_cast<uint32_t*>(ws + c.ev),
-                                         reinterpret_cast<uint16_t*>(ws + c.hist), d_nii, d_bits, d_iters, st);
-    } else {
-        if (h->fwin.window)
-            e = td::launch_fixed_window(a, td::fx::FxWindow{h->fwin.window, h->fwin.overlap}, m, d_nii, d_bits, st);
-        else
-            e = td::launch_fixed_turbo(a, m, d_bits, st);
-        if (e == hipSuccess && d_iters)   // no rule (td_set_fixed_stop): every codeword takes them all
-            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
-    }
+    // the schedule's rule: a fixed handle has one of the two at most (td_set_fixed_stop needs window 0)
+    const td_stop_params& rule = h->fwin.window ? h->fwstop : h->fstop;
+    const bool hda = rule.rule == TD_STOP_HDA;
+    td::fx::FxStop s{};
+    s.rule = rule.rule;
+    s.first = std::max(hda ? 2 : 1, rule.min_iters);
+    s.syn = hda ? nullptr : reinterpret_cast<const int*>(h->d_crc);
+    s.used = reinterpret_cast<int32_t*>(ws + c.used);
+    const td::fx::FxWindow w{h->fwin.window, h->fwin.overlap};
+    const bool stops = rule.rule != TD_STOP_NONE;
+    e = td::launch_fixed_decode(a, w.window ? &w : nullptr, stops ? &s : nullptr, m, reinterpret_cast<uint32_t*>(ws + c.ev),
+                                reinterpret_cast<uint16_t*>(ws + c.hist), d_nii, d_bits, d_iters, st);
+    if (e == hipSuccess && !stops && d_iters)   // no rule: every codeword takes them all
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_iters), h->p.iterations, (size_t)B, st);
     if (e != hipSuccess) return hip_fail(e, "launch_fixed_turbo");
     h->clk_valid = false;
     if (ev) {
@@ -1194,29 +1181,34 @@ int td_set_window_stop(td_handle* h, const td_stop_params* s)
     return TD_OK;
 }
 
-int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
+// td_set_fixed_stop and td_set_fixed_window_stop: `who` is the entry point, `rule` the handle's member that it
+// sets, `window` the schedule that it needs and `other` its message on a handle with the other one.  The
+// sub-block setter refuses a handle without a window before anything else, the rule's off included; the
+// exact one refuses a window only for a rule that it would otherwise set.
+static int set_fixed_rule(td_handle* h, const td_stop_params* s, const std::string& who, td_stop_params td_handle::*rule,
+                          bool window, const char* other)
 {
-    if (!h) return fail(TD_EINVAL, "td_set_fixed_stop: null handle");
-    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_stop: the handle is not fixed-point (TD_FIXED)");
+    if (!h) return fail(TD_EINVAL, who + ": null handle");
+    if (!is_fixed(h)) return fail(TD_EINVAL, who + ": the handle is not fixed-point (TD_FIXED)");
+    const bool wrong = (h->fwin.window != 0) != window;
+    if (window && wrong) return fail(TD_EINVAL, who + other);
     if (!s || s->rule == TD_STOP_NONE) {
-        h->fstop = td_stop_params{TD_STOP_NONE, 1, 0};
+        h->*rule = td_stop_params{TD_STOP_NONE, 1, 0};
         return TD_OK;
     }
-    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, "td_set_fixed_stop: unknown rule");
-    if (h->fwin.window)
-        return fail(TD_EINVAL, "td_set_fixed_stop: the TD_FIXED handle has a sub-block schedule (td_set_fixed_window); "
-                               "its rule is set by td_set_fixed_window_stop");
+    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC) return fail(TD_EINVAL, who + ": unknown rule");
+    if (wrong) return fail(TD_EINVAL, who + other);
     if (s->min_iters < 1 || s->min_iters > h->p.iterations)
-        return fail(TD_EINVAL, "td_set_fixed_stop: min_iters must be in [1, iterations]");
+        return fail(TD_EINVAL, who + ": min_iters must be in [1, iterations]");
     if (s->rule == TD_STOP_CRC) {
         if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
-            return fail(TD_EINVAL, "td_set_fixed_stop: crc_poly must be the 24 low-order coefficients, non-zero");
-        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_fixed_stop: TD_STOP_CRC needs K > 24");
+            return fail(TD_EINVAL, who + ": crc_poly must be the 24 low-order coefficients, non-zero");
+        if (h->p.K <= 24) return fail(TD_EINVAL, who + ": TD_STOP_CRC needs K > 24");
         TD_HIP(hipSetDevice(h->p.device));
         // the table lives on the device from here on: a decode allocates nothing for the rule
         if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
             h->d_crc = nullptr;
-            return fail(TD_ENOMEM, "td_set_fixed_stop: hipMalloc failed");
+            return fail(TD_ENOMEM, who + ": hipMalloc failed");
         }
         std::vector<uint32_t> syn((size_t)h->p.K), tab((size_t)h->p.K);
         td::crc24_syndromes(h->p.K, s->crc_poly, syn.data());
@@ -1224,43 +1216,22 @@ int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
         TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
         TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    h->fstop = *s;
+    h->*rule = *s;
     return TD_OK;
+}
+
+int td_set_fixed_stop(td_handle* h, const td_stop_params* s)
+{
+    return set_fixed_rule(h, s, "td_set_fixed_stop", &td_handle::fstop, false,
+                          ": the TD_FIXED handle has a sub-block schedule (td_set_fixed_window); "
+                          "its rule is set by td_set_fixed_window_stop");
 }
 
 int td_set_fixed_window_stop(td_handle* h, const td_stop_params* s)
 {
-    if (!h) return fail(TD_EINVAL, "td_set_fixed_window_stop: null handle");
-    if (!is_fixed(h)) return fail(TD_EINVAL, "td_set_fixed_window_stop: the handle is not fixed-point (TD_FIXED)");
-    if (!h->fwin.window)
-        return fail(TD_EINVAL, "td_set_fixed_window_stop: the TD_FIXED handle's schedule is not the sub-block one "
-                               "(td_set_fixed_window first; the exact schedule's rule is td_set_fixed_stop)");
-    if (!s || s->rule == TD_STOP_NONE) {
-        h->fwstop = td_stop_params{TD_STOP_NONE, 1, 0};
-        return TD_OK;
-    }
-    if (s->rule != TD_STOP_HDA && s->rule != TD_STOP_CRC)
-        return fail(TD_EINVAL, "td_set_fixed_window_stop: unknown rule");
-    if (s->min_iters < 1 || s->min_iters > h->p.iterations)
-        return fail(TD_EINVAL, "td_set_fixed_window_stop: min_iters must be in [1, iterations]");
-    if (s->rule == TD_STOP_CRC) {
-        if (s->crc_poly == 0 || (s->crc_poly & ~td::kCrc24Mask))
-            return fail(TD_EINVAL, "td_set_fixed_window_stop: crc_poly must be the 24 low-order coefficients, non-zero");
-        if (h->p.K <= 24) return fail(TD_EINVAL, "td_set_fixed_window_stop: TD_STOP_CRC needs K > 24");
-        TD_HIP(hipSetDevice(h->p.device));
-        // the table lives on the device from here on: a decode allocates nothing for the rule
-        if (!h->d_crc && hipMalloc(reinterpret_cast<void**>(&h->d_crc), (size_t)h->p.K * sizeof(uint32_t)) != hipSuccess) {
-            h->d_crc = nullptr;
-            return fail(TD_ENOMEM, "td_set_fixed_window_stop: hipMalloc failed");
-        }
-        std::vector<uint32_t> syn((size_t)h->p.K), tab((size_t)h->p.K);
-        td::crc24_syndromes(h->p.K, s->crc_poly, syn.data());
-        for (int i = 0; i < h->p.K; ++i) tab[i] = syn[h->pi[i]];   // in the order SISO2 meets the bits (FxStop)
-        TD_HIP(hipDeviceSynchronize());   // no decode of this handle still reads the previous table
-        TD_HIP(hipMemcpy(h->d_crc, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    h->fwstop = *s;
-    return TD_OK;
+    return set_fixed_rule(h, s, "td_set_fixed_window_stop", &td_handle::fwstop, true,
+                          ": the TD_FIXED handle's schedule is not the sub-block one "
+                          "(td_set_fixed_window first; the exact schedule's rule is td_set_fixed_stop)");
 }
 
 uint32_t td_crc24_host(const uint8_t* bits, int K, uint32_t poly)

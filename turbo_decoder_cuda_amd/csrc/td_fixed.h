@@ -61,27 +61,19 @@ inline size_t fx_nii_bytes(int B, int K, int window)
 // links, and the fixed entry points then fail with TD_EHIP.  libturbo_mi355x.so always has them.
 // d_q [B][3K+12] int8 -> xs / xp1 / xp2 of the workspace (-128 read as -127, the padding zeroed)
 __attribute__((weak)) hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st);
-// The four decodes below take m, td_set_fixed_maxstar's table or null: with a table they launch the kernels
-// instantiated with fx::MaxStar, without one the Max-Log-MAP kernels.
-// all iterations of all codewords, then bitsT -> d_bits ([B][K] or [B][iters][K])
-__attribute__((weak)) hipError_t launch_fixed_turbo(const fx::FxArgs& p, const fx::MaxStar* m, uint8_t* d_bits,
-                                                    hipStream_t st);
-// the same with early termination: a codeword's rows past its stop are copies of its stop row, d_bits
-// without all_iters is its stop row, and d_iters (nullable, [B]) gets s.used
-__attribute__((weak)) hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, const fx::MaxStar* m,
-                                                         uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
-// the sub-block schedule (td_set_fixed_window): a launch per SISO and iteration on st, grid (Bp / kFxLanes) x
-// sub-blocks, then bitsT -> d_bits as launch_fixed_turbo.  d_nii: the state of td_set_fixed_window_nii
-// (fx::nii_words words, right after the carve's total), or null: off, the kernels without it
-__attribute__((weak)) hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m,
-                                                     uint32_t* d_nii, uint8_t* d_bits, hipStream_t st);
-// the sub-block schedule with early termination (td_set_fixed_window_stop): s.used is reset on st, then per
-// iteration SISO1, SISO2 and the judge, then the frozen rows and d_iters as launch_fixed_turbo_stop; d_ev and
-// d_hist are the carve's ev and hist, d_nii as for launch_fixed_window
-__attribute__((weak)) hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s,
-                                                          const fx::MaxStar* m, uint32_t* d_ev, uint16_t* d_hist,
-                                                          uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters,
-                                                          hipStream_t st);
+// One decode on st, then bitsT -> d_bits ([B][K] or [B][iters][K]).  The optional parts are nullable:
+//   w       the sub-block schedule (td_set_fixed_window): a launch per SISO and iteration, grid (Bp / kFxLanes) x
+//           sub-blocks; null: the exact schedule, all iterations of all codewords in one launch
+//   s       early termination (td_set_fixed_stop / td_set_fixed_window_stop): a codeword's rows past its stop are
+//           copies of its stop row, d_bits without all_iters is its stop row, and d_iters (nullable, [B]) gets
+//           s->used; on the sub-block schedule s->used is reset on st, every iteration ends with the judge's
+//           launch, and d_ev and d_hist are the carve's ev and hist.  null: no rule, d_iters is not written
+//   m       td_set_fixed_maxstar's table: the kernels instantiated with fx::MaxStar; null: Max-Log-MAP
+//   d_nii   the state of td_set_fixed_window_nii (fx::nii_words words, right after the carve's total); null: off
+// A part that is null launches the kernels without it.
+__attribute__((weak)) hipError_t launch_fixed_decode(const fx::FxArgs& p, const fx::FxWindow* w, const fx::FxStop* s,
+                                                     const fx::MaxStar* m, uint32_t* d_ev, uint16_t* d_hist,
+                                                     uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters, hipStream_t st);
 // saturating int8 de-rate-matching: d_e [B][E] -> d_out [B][3K+12]
 __attribute__((weak)) hipError_t launch_fixed_dematch(const RmParams& p, const int8_t* d_e, int8_t* d_out,
                                                       int accumulate, hipStream_t st);

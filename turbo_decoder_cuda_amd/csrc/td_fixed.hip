@@ -5,38 +5,38 @@
 //   fx_demux_kernel    q [B][3K+12] -> xs, xp1, xp2 [row][Bp]: a 64 x 64 byte transpose through LDS, so
 //                      that both the reads (along the stream) and the writes (along the batch) are
 //                      contiguous; -128 becomes -127 and the lanes of the padding get zeros.
-//   fx_turbo_kernel    one codeword per lane, all iterations in one launch.  A lane keeps its eight
-//                      state metrics in registers (int32, never normalised); the forward pass leaves
-//                      alpha at every kW-th step in the workspace (32 B per kW steps and codeword), the
-//                      backward pass recomputes a window's alpha rows into registers and runs beta,
+//   fx_turbo_kernel<STOP, M>  the exact schedule: one codeword per lane, all iterations in one launch.  A
+//                      lane keeps its eight state metrics in registers (int32, never normalised); the forward
+//                      pass leaves alpha at every kW-th step in the workspace (32 B per kW steps and codeword),
+//                      the backward pass recomputes a window's alpha rows into registers and runs beta,
 //                      Lambda and the extrinsic over them.  The interleaver is a row index that the
 //                      whole wave shares, so every access to the workspace is one contiguous row piece.
+//                      STOP (td_set_fixed_stop): a lane whose codeword has stopped is skipped, a wave whose
+//                      lanes have all stopped returns.
+//   fx_window_siso_kernel<DEC, STOP, NII, M>  the sub-block schedule (td_set_fixed_window): one SISO of one
+//                      iteration a launch, a wave = 64 codewords x one sub-block (blockIdx.y), the kernel
+//                      boundary as the ordering between a SISO's extrinsic writes and the next SISO's reads.
+//                      STOP (td_set_fixed_window_stop): used[b] is the state (0 = running), a wave with no
+//                      running codeword returns, SISO2 leaves each sub-block's evidence in the workspace (and,
+//                      for the next iteration's HDA comparison, every 16-step window's decisions packed).
+//                      NII (td_set_fixed_window_nii): the state's two halves (read: the previous iteration's,
+//                      written: this one's) are the kernel's FxNii.
+//   fx_window_judge_kernel  a launch of its own after SISO2's of a stopping sub-block decode: folds the
+//                      evidence and stops the codeword.
 //   fx_bits_kernel     bitsT [rows][K][Bp] -> the caller's [B][rows][K], the transpose back.
-//   fx_turbo_stop_kernel, fx_bits_stop_kernel  the same two with early termination (td_set_fixed_stop): a
-//                      lane whose codeword has stopped is skipped, a wave whose lanes have all stopped
-//                      returns, and the transpose back reads row min(row, used - 1) and undoes the interleaved
-//                      order that the stopping decoder keeps its decisions in.
-//   fx_window_siso_kernel  the sub-block schedule (td_set_fixed_window): one SISO of one iteration a launch,
-//                      a wave = 64 codewords x one sub-block (blockIdx.y), the kernel boundary as the
-//                      ordering between a SISO's extrinsic writes and the next SISO's reads.
-//   fx_window_siso_stop_kernel, fx_window_judge_kernel  the sub-block schedule with early termination
-//                      (td_set_fixed_window_stop): used[b] is the state (0 = running), a wave with no running
-//                      codeword returns, SISO2 leaves each sub-block's evidence in the workspace (and, for
-//                      the next iteration's HDA comparison, every 16-step window's decisions packed) and the
-//                      judge, a launch of its own after SISO2's, folds it and stops the codeword; then
-//                      fx_bits_stop_kernel.
-//   fx_turbo_maxstar_kernel, fx_turbo_stop_maxstar_kernel, fx_window_siso_maxstar_kernel,
-//   fx_window_siso_stop_maxstar_kernel  the decoding kernels above with td_set_fixed_maxstar's table: the lane
-//                      code instantiated with fx::MaxStar for fx::MaxLog, the table's two words and its shift
-//                      as kernel arguments (scalar registers).  Launched only while a table is set; without
-//                      one a decode launches the kernels above, which do not change.
-//   fx_window_siso_nii_kernel, fx_window_siso_stop_nii_kernel, fx_window_siso_maxstar_nii_kernel,
-//   fx_window_siso_stop_maxstar_nii_kernel  the four sub-block kernels with next-iteration initialisation
-//                      (td_set_fixed_window_nii): the lane code instantiated with NII, the state's two halves
-//                      (read: the previous iteration's, written: this one's) as kernel arguments.  Launched
-//                      only while NII is on; with it off a decode launches the kernels above, which do not change.
+//   fx_bits_stop_kernel  the same after a stopping decode: reads row min(row, used - 1) and undoes the
+//                      interleaved order that the stopping decoders keep their decisions in.
 //   fx_dematch_kernel  saturating int8 de-rate-matching, one thread per stream position.
+//
+// The two decoding templates are the lane code of td_fixed_core.h instantiated by the handle's settings: M is
+// fx::MaxLog, or fx::MaxStar while td_set_fixed_maxstar's table is set.  Each has one argument list whatever
+// the instantiation -- FxArgs, then the schedule's structs --, an argument that the instantiation does not use
+// is passed zeroed and never read, and launch_fixed_decode picks the instantiation: a setting that is off
+// launches the kernel without it.  The table's two words and its shift are kernel arguments (scalar
+// registers) in every instantiation; MaxLog is built in the kernel.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "td_fixed.h"
 
@@ -85,9 +85,25 @@ __global__ __launch_bounds__(kTileThreads) void fx_demux_kernel(const int8_t* __
     }
 }
 
-__global__ __launch_bounds__(kFxLanes) void fx_turbo_kernel(fx::FxArgs p)
+// the max of instantiation M: the table of the kernel's arguments, or the plain max
+template <class M>
+__device__ __forceinline__ M max_of(const fx::MaxStar& m)
 {
-    fx::decode_codeword(p, blockIdx.x * kFxLanes + threadIdx.x);
+    if constexpr (M::kTable)
+        return m;
+    else
+        return M();
+}
+
+// The exact schedule.  STOP (td_set_fixed_stop): a wave ends once its 64 codewords have stopped.
+template <bool STOP, class M>
+__global__ __launch_bounds__(kFxLanes) void fx_turbo_kernel(fx::FxArgs p, fx::FxStop s, fx::MaxStar m)
+{
+    const size_t b = blockIdx.x * kFxLanes + threadIdx.x;
+    if (STOP)
+        fx::decode_codeword_stop(p, s, b, max_of<M>(m));
+    else
+        fx::decode_codeword(p, b, max_of<M>(m));
 }
 
 __global__ __launch_bounds__(kTileThreads) void fx_bits_kernel(const uint8_t* __restrict__ bitsT, int K, int B, size_t Bp,
@@ -104,12 +120,6 @@ __global__ __launch_bounds__(kTileThreads) void fx_bits_kernel(const uint8_t* __
         const size_t b = b0 + c;
         if (b < (size_t)B && k0 + tx < K) bits[(b * rows + row) * (size_t)K + k0 + tx] = tile[tx][c];
     }
-}
-
-// The stopping decoder (td_set_fixed_stop): a wave ends once its 64 codewords have stopped.
-__global__ __launch_bounds__(kFxLanes) void fx_turbo_stop_kernel(fx::FxArgs p, fx::FxStop s)
-{
-    fx::decode_codeword_stop(p, s, blockIdx.x * kFxLanes + threadIdx.x);
 }
 
 // fx_bits_kernel after a stopping decode: bitsT holds rows 0 .. used[b] - 1 of codeword b by interleaved
@@ -145,20 +155,17 @@ __global__ __launch_bounds__(kTileThreads) void fx_bits_stop_kernel(const uint8_
 // The sub-block index is the block's, so the interleaver entries stay scalar loads and every row access one
 // contiguous piece.  SISO1 reads ext21 and writes ext12, SISO2 the reverse (and bitsT): no launch
 // reads an array that it writes, apart from a sub-block's own checkpoint slots.
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_kernel(fx::FxArgs p, fx::FxWindow w, int it)
+// STOP (td_set_fixed_window_stop), on the same grid: a wave whose 64 codewords have all stopped returns at
+// once, and SISO2 leaves the sub-block's evidence at ev[blockIdx.y][b].  NII (td_set_fixed_window_nii): n, the
+// same in every lane.
+template <int DEC, bool STOP, bool NII, class M>
+__global__ __launch_bounds__(kFxLanes) void fx_window_siso_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
+                                                                   fx::MaxStar m, fx::FxNii n,
+                                                                   uint32_t* __restrict__ ev,
+                                                                   uint16_t* __restrict__ hist, int it)
 {
-    fx::siso_window_pass<DEC>(p, w, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
-}
-
-// The same with early termination (td_set_fixed_window_stop), on the same grid: a wave whose 64 codewords
-// have all stopped returns at once, and SISO2 leaves the sub-block's evidence at ev[blockIdx.y][b].
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
-                                                                        uint32_t* __restrict__ ev,
-                                                                        uint16_t* __restrict__ hist, int it)
-{
-    fx::siso_window_stop<DEC>(p, w, s, ev, hist, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
+    fx::siso_window_pass<DEC, STOP, NII>(p, w, s, ev, hist, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y,
+                                         max_of<M>(m));
 }
 
 // One thread per codeword after SISO2's launch of iteration `it`: folds the sub-blocks' evidence and
@@ -168,65 +175,6 @@ __global__ __launch_bounds__(kTileThreads) void fx_window_judge_kernel(fx::FxArg
                                                                        const uint32_t* __restrict__ ev, int nS, int it)
 {
     fx::window_judge(p, s, ev, nS, (size_t)blockIdx.x * kTileThreads + threadIdx.x, it);
-}
-
-// The four decoding kernels with the correction table (td_set_fixed_maxstar): the same grids and arguments,
-// and m, the same in every lane.
-__global__ __launch_bounds__(kFxLanes) void fx_turbo_maxstar_kernel(fx::FxArgs p, fx::MaxStar m)
-{
-    fx::decode_codeword(p, blockIdx.x * kFxLanes + threadIdx.x, m);
-}
-
-__global__ __launch_bounds__(kFxLanes) void fx_turbo_stop_maxstar_kernel(fx::FxArgs p, fx::FxStop s, fx::MaxStar m)
-{
-    fx::decode_codeword_stop(p, s, blockIdx.x * kFxLanes + threadIdx.x, m);
-}
-
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_maxstar_kernel(fx::FxArgs p, fx::FxWindow w, fx::MaxStar m,
-                                                                           int it)
-{
-    fx::siso_window_pass<DEC>(p, w, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
-}
-
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_maxstar_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
-                                                                                fx::MaxStar m, uint32_t* __restrict__ ev,
-                                                                                uint16_t* __restrict__ hist, int it)
-{
-    fx::siso_window_stop<DEC>(p, w, s, ev, hist, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
-}
-
-// The four sub-block kernels with next-iteration initialisation (td_set_fixed_window_nii): the same grids, and
-// n, the same in every lane.
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxNii n, int it)
-{
-    fx::siso_window_pass_nii<DEC>(p, w, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
-}
-
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::FxStop s,
-                                                                            fx::FxNii n, uint32_t* __restrict__ ev,
-                                                                            uint16_t* __restrict__ hist, int it)
-{
-    fx::siso_window_stop_nii<DEC>(p, w, s, ev, hist, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y);
-}
-
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_maxstar_nii_kernel(fx::FxArgs p, fx::FxWindow w, fx::MaxStar m,
-                                                                               fx::FxNii n, int it)
-{
-    fx::siso_window_pass_nii<DEC>(p, w, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
-}
-
-template <int DEC>
-__global__ __launch_bounds__(kFxLanes) void fx_window_siso_stop_maxstar_nii_kernel(fx::FxArgs p, fx::FxWindow w,
-                                                                                    fx::FxStop s, fx::MaxStar m, fx::FxNii n,
-                                                                                    uint32_t* __restrict__ ev,
-                                                                                    uint16_t* __restrict__ hist, int it)
-{
-    fx::siso_window_stop_nii<DEC>(p, w, s, ev, hist, n, blockIdx.x * kFxLanes + threadIdx.x, it, (int)blockIdx.y, m);
 }
 
 // The owner of stream position q adds its e in ascending k, saturating to [-127, 127] after every
@@ -259,6 +207,16 @@ __global__ __launch_bounds__(kTileThreads) void fx_dematch_kernel(RmParams p, co
     }
 }
 
+// A runtime flag as a compile-time one: f(std::true_type()) or f(std::false_type()).
+template <class F>
+void with_flag(bool v, F&& f)
+{
+    if (v)
+        f(std::true_type());
+    else
+        f(std::false_type());
+}
+
 }  // namespace
 
 hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_t st)
@@ -270,100 +228,58 @@ hipError_t launch_fixed_demux(const fx::FxArgs& p, const int8_t* d_q, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_fixed_turbo(const fx::FxArgs& p, const fx::MaxStar* m, uint8_t* d_bits, hipStream_t st)
+hipError_t launch_fixed_decode(const fx::FxArgs& p, const fx::FxWindow* w, const fx::FxStop* s, const fx::MaxStar* m,
+                               uint32_t* d_ev, uint16_t* d_hist, uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters,
+                               hipStream_t st)
 {
-    if (m)
-        hipLaunchKernelGGL(fx_turbo_maxstar_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, *m);
-    else
-        hipLaunchKernelGGL(fx_turbo_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int rows = p.all_iters ? p.iters : 1;
-    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
-    hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
-    return hipGetLastError();
-}
-
-hipError_t launch_fixed_turbo_stop(const fx::FxArgs& p, const fx::FxStop& s, const fx::MaxStar* m, uint8_t* d_bits,
-                                   int32_t* d_iters, hipStream_t st)
-{
-    if (m)
-        hipLaunchKernelGGL(fx_turbo_stop_maxstar_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s, *m);
-    else
-        hipLaunchKernelGGL(fx_turbo_stop_kernel, dim3((unsigned)(p.Bp / kFxLanes)), dim3(kFxLanes), 0, st, p, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int rows = p.all_iters ? p.iters : 1;
-    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
-    hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s.used, p.pinv, p.K, p.B, p.Bp,
-                       rows, p.iters, d_bits, d_iters);
-    return hipGetLastError();
-}
-
-hipError_t launch_fixed_window(const fx::FxArgs& p, const fx::FxWindow& w, const fx::MaxStar* m, uint32_t* d_nii,
-                               uint8_t* d_bits, hipStream_t st)
-{
-    const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)fx::window_blocks(p.L, w.window));
-    for (int it = 0; it < p.iters; ++it) {
-        if (d_nii) {
-            const fx::FxNii n0 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 0), n1 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 1);
-            if (m) {
-                hipLaunchKernelGGL(fx_window_siso_maxstar_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, n0, it);
-                hipLaunchKernelGGL(fx_window_siso_maxstar_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, n1, it);
-            } else {
-                hipLaunchKernelGGL(fx_window_siso_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, n0, it);
-                hipLaunchKernelGGL(fx_window_siso_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, n1, it);
-            }
-        } else if (m) {
-            hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
-            hipLaunchKernelGGL(fx_window_siso_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, *m, it);
-        } else {
-            hipLaunchKernelGGL(fx_window_siso_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
-            hipLaunchKernelGGL(fx_window_siso_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, it);
+    const fx::FxStop stop = s ? *s : fx::FxStop{};     // what a setting that is off leaves zeroed is never read
+    const fx::MaxStar tab = m ? *m : fx::MaxStar{};
+    const dim3 lanes(kFxLanes);
+    // the instantiation of the handle's settings: f(STOP, NII, M) with the flags as types
+    auto pick = [&](auto&& f) {
+        with_flag(s != nullptr, [&](auto STOP) {
+            with_flag(d_nii != nullptr, [&](auto NII) {
+                with_flag(m != nullptr, [&](auto TAB) {
+                    f(STOP, NII, std::conditional_t<decltype(TAB)::value, fx::MaxStar, fx::MaxLog>());
+                });
+            });
+        });
+    };
+    if (!w) {
+        const dim3 grid((unsigned)(p.Bp / kFxLanes));
+        pick([&](auto STOP, auto, auto M) {
+            hipLaunchKernelGGL((fx_turbo_kernel<decltype(STOP)::value, decltype(M)>), grid, lanes, 0, st, p, stop, tab);
+        });
+    } else {
+        if (s) {
+            hipError_t e = hipMemsetAsync(s->used, 0, p.Bp * sizeof(int32_t), st);   // every codeword runs
+            if (e != hipSuccess) return e;
+        }
+        const int nS = fx::window_blocks(p.L, w->window);
+        const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)nS);
+        const dim3 jgrid((unsigned)((p.Bp + kTileThreads - 1) / kTileThreads));
+        for (int it = 0; it < p.iters; ++it) {
+            const fx::FxNii n0 = d_nii ? fx::nii_args(d_nii, p.L, *w, p.Bp, it, 0) : fx::FxNii{};
+            const fx::FxNii n1 = d_nii ? fx::nii_args(d_nii, p.L, *w, p.Bp, it, 1) : fx::FxNii{};
+            pick([&](auto STOP, auto NII, auto M) {
+                constexpr bool S = decltype(STOP)::value, N = decltype(NII)::value;
+                hipLaunchKernelGGL((fx_window_siso_kernel<0, S, N, decltype(M)>), wgrid, lanes, 0, st, p, *w, stop, tab, n0,
+                                   d_ev, d_hist, it);
+                hipLaunchKernelGGL((fx_window_siso_kernel<1, S, N, decltype(M)>), wgrid, lanes, 0, st, p, *w, stop, tab, n1,
+                                   d_ev, d_hist, it);
+            });
+            if (s) hipLaunchKernelGGL(fx_window_judge_kernel, jgrid, dim3(kTileThreads), 0, st, p, stop, d_ev, nS, it);
         }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int rows = p.all_iters ? p.iters : 1;
     const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
-    hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
-    return hipGetLastError();
-}
-
-hipError_t launch_fixed_window_stop(const fx::FxArgs& p, const fx::FxWindow& w, const fx::FxStop& s, const fx::MaxStar* m,
-                                    uint32_t* d_ev, uint16_t* d_hist, uint32_t* d_nii, uint8_t* d_bits, int32_t* d_iters,
-                                    hipStream_t st)
-{
-    hipError_t e = hipMemsetAsync(s.used, 0, p.Bp * sizeof(int32_t), st);   // every codeword runs
-    if (e != hipSuccess) return e;
-    const int nS = fx::window_blocks(p.L, w.window);
-    const dim3 wgrid((unsigned)(p.Bp / kFxLanes), (unsigned)nS);
-    const dim3 jgrid((unsigned)((p.Bp + kTileThreads - 1) / kTileThreads));
-    for (int it = 0; it < p.iters; ++it) {
-        if (d_nii) {
-            const fx::FxNii n0 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 0), n1 = fx::nii_args(d_nii, p.L, w, p.Bp, it, 1);
-            if (m) {
-                hipLaunchKernelGGL(fx_window_siso_stop_maxstar_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, n0, d_ev, d_hist, it);
-                hipLaunchKernelGGL(fx_window_siso_stop_maxstar_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, n1, d_ev, d_hist, it);
-            } else {
-                hipLaunchKernelGGL(fx_window_siso_stop_nii_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, n0, d_ev, d_hist, it);
-                hipLaunchKernelGGL(fx_window_siso_stop_nii_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, n1, d_ev, d_hist, it);
-            }
-        } else if (m) {
-            hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
-            hipLaunchKernelGGL(fx_window_siso_stop_maxstar_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, *m, d_ev, d_hist, it);
-        } else {
-            hipLaunchKernelGGL(fx_window_siso_stop_kernel<0>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
-            hipLaunchKernelGGL(fx_window_siso_stop_kernel<1>, wgrid, dim3(kFxLanes), 0, st, p, w, s, d_ev, d_hist, it);
-        }
-        hipLaunchKernelGGL(fx_window_judge_kernel, jgrid, dim3(kTileThreads), 0, st, p, s, d_ev, nS, it);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int rows = p.all_iters ? p.iters : 1;
-    const dim3 grid((unsigned)((p.K + kTile - 1) / kTile), (unsigned)(p.Bp / kTile), (unsigned)rows);
-    hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s.used, p.pinv, p.K, p.B, p.Bp,
-                       rows, p.iters, d_bits, d_iters);
+    if (s)
+        hipLaunchKernelGGL(fx_bits_stop_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, s->used, p.pinv, p.K, p.B, p.Bp,
+                           rows, p.iters, d_bits, d_iters);
+    else
+        hipLaunchKernelGGL(fx_bits_kernel, grid, dim3(kTileThreads), 0, st, p.bitsT, p.K, p.B, p.Bp, rows, d_bits);
     return hipGetLastError();
 }
 

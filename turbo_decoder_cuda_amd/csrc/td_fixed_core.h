@@ -56,7 +56,7 @@ struct FxArgs {
 };
 
 // Early termination (td_set_fixed_stop, and td_set_fixed_window_stop on the sub-block schedule), next to
-// FxArgs and not in it: tests/fixed_core_host.cpp initialises FxArgs member by member.
+// FxArgs and not in it: tests/fixed_host_common.h initialises FxArgs member by member.
 struct FxStop {
     int rule;             // 1: the rows repeat (HDA), 2: the row's CRC-24 is zero (enum td_stop_rule)
     int first;            // the smallest iteration count a codeword may stop after: max(HDA ? 2 : 1, min_iters)
@@ -155,6 +155,24 @@ TDF_HD void alpha_step(const int (&a)[8], int S, int P, int (&n)[8], const M& mx
     }
 }
 
+TDF_HD void copy8(int (&a)[8], const int (&n)[8])
+{
+#pragma unroll
+    for (int s = 0; s < 8; ++s) a[s] = n[s];
+}
+
+// One beta step backwards over position i's branch metrics, without an output (the warm-up).
+template <class M = MaxLog>
+TDF_HD void beta_step(int (&bt)[8], int S, int P, const M& mx = M())
+{
+    int c[4];
+    gammas(S, P, c);
+    int n[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) n[s] = mx(c[gsel(s, 0)] + bt[next_state(s, 0)], c[gsel(s, 1)] + bt[next_state(s, 1)]);
+    copy8(bt, n);
+}
+
 // S = xs + La and P = xp of position i (i < L) of SISO `DEC` in iteration `it`
 template <int DEC>
 TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
@@ -177,131 +195,30 @@ TDF_HD void load_step(const FxArgs& p, size_t b, int it, int i, int& S, int& P)
     }
 }
 
-// One terminated pass of codeword b (Max-Log-MAP, or log-MAP with mx a MaxStar) with everything that follows it in the iteration:
-// the extrinsic (ext12 / ext21 and the caller's Le), and after SISO2 the hard decisions.
-//
-// STOP (the stopping decoder, sp its rule): SISO2 writes row `it` of bitsT in every iteration and returns
-// the rule's evidence on it, zero where the codeword may stop.  Both rules hold in any fixed order of
-// the bits, so the stopping decoder keeps bitsT in SISO2's own order, by interleaved position i: the
-// stores and the rule need no entry of pi (a scalar load and its wait in every step otherwise), and
-// the transpose back undoes the order (fx_bits_stop_kernel reads row pinv[k]).  HDA: the window's bits
-// of row it - 1 are loaded with the window's inputs -- sixteen loads in flight ahead of the
-// arithmetic, not one per step behind a store that the compiler must assume aliases it -- packed one
-// bit a step into a register, and compared with the window's new bits at its end.  CRC: the lane XORs
-// in the syndrome of every 1 bit, from a table in the same order.  The state is the evidence and two
-// bit masks; the previous row stays in the workspace.  Iterations before sp->first are not judged.
-template <int DEC, bool STOP, class M = MaxLog>
-TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it, const M& mx = M())
+// alpha over the sixteen positions from i, their loads ahead of the arithmetic
+template <int DEC, class M>
+TDF_HD void alpha_block(const FxArgs& p, size_t b, int it, int i, int (&a)[8], const M& mx)
 {
-    const int L = p.L, K = p.K;
-    const int nW = (L + kW - 1) / kW;
-    const bool live = b < (size_t)p.B;   // a lane of the padding decodes zeros and stores nothing outside the workspace
-
-    // forward: alpha at every window start
-    {
-        int a[8];
+    int S[kW], P[kW];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) a[s] = s ? kNeg : 0;
-        for (int w = 0; w < nW; ++w) {
+    for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i + t, S[t], P[t]);
 #pragma unroll
-            for (int s = 0; s < 8; ++s) p.ckpt[((size_t)w * 8 + s) * p.Bp + b] = a[s];
-            if (w == nW - 1) break;   // a window that is not the last is whole
-            int S[kW], P[kW];
-#pragma unroll
-            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, w * kW + t, S[t], P[t]);
-#pragma unroll
-            for (int t = 0; t < kW; ++t) {
-                int n[8];
-                alpha_step(a, S[t], P[t], n, mx);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) a[s] = n[s];
-            }
-        }
+    for (int t = 0; t < kW; ++t) {
+        int n[8];
+        alpha_step(a, S[t], P[t], n, mx);
+        copy8(a, n);
     }
-
-    // backward: per window, alpha again from its checkpoint, then beta and the outputs
-    int bt[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) bt[s] = s ? kNeg : 0;
-    const int row = STOP || p.all_iters ? it : 0;
-    const bool want_bits = DEC == 1 && (STOP || p.all_iters || it == p.iters - 1);
-    const bool judge = STOP && DEC == 1 && it + 1 >= sp->first;
-    int acc = 0;
-    for (int w = nW - 1; w >= 0; --w) {
-        const int i0 = w * kW;
-        int S[kW], P[kW];
-#pragma unroll
-        for (int t = 0; t < kW; ++t) {
-            const int i = i0 + t < L ? i0 + t : L - 1;   // past the end (last window): a valid row, never used
-            load_step<DEC>(p, b, it, i, S[t], P[t]);
-        }
-        unsigned was = 0, now = 0;   // HDA: bit t = the bit of position i0 + t in row it - 1, in row it
-        if (STOP && judge && sp->rule == 1) {
-            const uint8_t* prev = p.bitsT + (size_t)(row - 1) * K * p.Bp + b;   // first >= 2: row it - 1 exists
-#pragma unroll
-            for (int t = 0; t < kW; ++t) {   // no branch per step: sixteen loads in flight, the tail's masked off
-                const int i = i0 + t < K ? i0 + t : K - 1;
-                was |= (unsigned)prev[(size_t)i * p.Bp] << t;
-            }
-            const int nv = K - i0;   // the window's positions below K
-            was &= nv >= kW ? (1u << kW) - 1 : nv > 0 ? (1u << nv) - 1 : 0u;
-        }
-        int A[kW][8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
-#pragma unroll
-        for (int t = 0; t + 1 < kW; ++t) alpha_step(A[t], S[t], P[t], A[t + 1], mx);
-#pragma unroll
-        for (int t = kW - 1; t >= 0; --t) {
-            const int i = i0 + t;
-            if (i < L) {
-                int c[4];
-                gammas(S[t], P[t], c);
-                int e0[8], e1[8];
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    e0[s] = c[gsel(s, 0)] + bt[next_state(s, 0)];
-                    e1[s] = c[gsel(s, 1)] + bt[next_state(s, 1)];
-                }
-                int m0 = A[t][0] + e0[0], m1 = A[t][0] + e1[0];
-#pragma unroll
-                for (int s = 1; s < 8; ++s) {
-                    m0 = mx(m0, A[t][s] + e0[s]);
-                    m1 = mx(m1, A[t][s] + e1[s]);
-                }
-                const int llr = half_lambda<M>(m1 - m0);
-                const int le = ext_f(llr - S[t], p.le_max, p.scale_q);
-                if (i < K) (DEC == 0 ? p.ext12 : p.ext21)[(size_t)i * p.Bp + b] = (int16_t)le;
-                if (p.le && live) p.le[(((size_t)b * p.iters + it) * 2 + DEC) * L + i] = (int16_t)le;
-                if (!STOP) {
-                    if (want_bits && i < K)
-                        p.bitsT[((size_t)row * K + (size_t)table_entry(p.pi, i)) * p.Bp + b] = llr < 0 ? 0 : 1;
-                } else if (want_bits && i < K) {
-                    const int bit = llr < 0 ? 0 : 1;
-                    p.bitsT[((size_t)row * K + (size_t)i) * p.Bp + b] = (uint8_t)bit;
-                    if (judge) {
-                        if (sp->rule == 1)
-                            now |= (unsigned)bit << t;
-                        else
-                            acc ^= -bit & table_entry(sp->syn, i);
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 8; ++s) bt[s] = mx(e0[s], e1[s]);
-            }
-        }
-        acc |= (int)(was ^ now);
-    }
-    return acc;
 }
 
-template <class M = MaxLog>
-TDF_HD void decode_codeword(const FxArgs& p, size_t b, const M& mx = M())
+// beta over the sixteen positions below i, i - 1 first (the warm-up), their loads ahead of the arithmetic
+template <int DEC, class M>
+TDF_HD void beta_block(const FxArgs& p, size_t b, int it, int i, int (&bt)[8], const M& mx)
 {
-    for (int it = 0; it < p.iters; ++it) {
-        siso_pass<0, false>(p, nullptr, b, it, mx);
-        siso_pass<1, false>(p, nullptr, b, it, mx);
-    }
+    int S[kW], P[kW];
+#pragma unroll
+    for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i - 1 - t, S[t], P[t]);
+#pragma unroll
+    for (int t = 0; t < kW; ++t) beta_step(bt, S[t], P[t], mx);
 }
 
 // The sub-block schedule (td_set_fixed_window), next to FxArgs and not in it, as FxStop is.
@@ -311,19 +228,6 @@ struct FxWindow {
 };
 
 constexpr int window_blocks(int L, int window) { return L / window > 1 ? L / window : 1; }
-
-// One beta step backwards over position i's branch metrics, without an output (the warm-up).
-template <class M = MaxLog>
-TDF_HD void beta_step(int (&bt)[8], int S, int P, const M& mx = M())
-{
-    int c[4];
-    gammas(S, P, c);
-    int n[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) n[s] = mx(c[gsel(s, 0)] + bt[next_state(s, 0)], c[gsel(s, 1)] + bt[next_state(s, 1)]);
-#pragma unroll
-    for (int s = 0; s < 8; ++s) bt[s] = n[s];
-}
 
 // Next-iteration initialisation (td_set_fixed_window_nii), next to FxArgs and not in it.  In iterations
 // after the first a warm-up that does not begin at a trellis end starts from the vector that the
@@ -385,28 +289,74 @@ TDF_HD void nii_load(const uint32_t* slot, size_t Bp, size_t b, int (&v)[8])
     }
 }
 
-// siso_pass for sub-block sb of the sub-block schedule: positions [sb W, (sb + 1) W), the last
-// sub-block up to L.  alpha warms up from max(sb W - overlap, 0) and beta from min(end + overlap, L);
-// a recursion that starts at the trellis' end starts from the terminated state, any other from equal
-// metrics (all 0: never normalised, so the sums stay inside the bounds at the head of this file).  The
-// warm-ups take any start: sixteen steps at a time with their loads ahead of the arithmetic, then the
-// rest one by one.  The sub-block's own steps are siso_pass's: alpha checkpoints at ckpt[w], w the
-// window's index in the whole trellis (sub-blocks own disjoint slots), then per window the recompute,
-// beta, Lambda, f and the stores.  sb must be the same in every lane of a wave.  Sub-blocks of one
-// SISO read ext / xs / xp anywhere and write only their own positions of the other ext array, so
-// they may run in any order or at once; the next SISO may start when all of them are done.
+// The positions one call of siso_span covers.  A span over [0, L) that starts at both ends of the trellis
+// is the exact schedule's pass; sub-block sb of the sub-block schedule is window_span's.
+struct FxSpan {
+    int start, end;       // the call's own positions, start a multiple of kW: a run of recomputation windows
+    int a_from, b_from;   // alpha warms up over [a_from, start) and beta over [end, b_from); a recursion that
+                          // starts at the trellis' end (a_from == 0, b_from == L) starts from the terminated state
+    int sb, nS, W;        // the sub-block's index, their number and their width: the row of ev, the slots of NII
+};
+
+// Sub-block sb: positions [sb W, (sb + 1) W), the last sub-block up to L.  alpha warms up from
+// max(sb W - overlap, 0) and beta from min(end + overlap, L).
+TDF_HD FxSpan window_span(int L, const FxWindow& wn, int sb)
+{
+    const int nS = window_blocks(L, wn.window);
+    const int start = sb * wn.window, end = sb == nS - 1 ? L : start + wn.window;
+    return FxSpan{start, end, start - wn.overlap <= 0 ? 0 : start - wn.overlap,
+                  end + wn.overlap >= L ? L : end + wn.overlap, sb, nS, wn.window};
+}
+
+// HDA's previous bits of the window at i0 for the exact stopping decoder: sixteen bytes of a row of bitsT
+// (prev is the row's entry of the lane's codeword), bit t = the bit of position i0 + t.  No branch per
+// step: sixteen loads in flight, the tail's masked off.
+TDF_HD unsigned row_bits(const uint8_t* prev, size_t Bp, int K, int i0)
+{
+    unsigned was = 0;
+#pragma unroll
+    for (int t = 0; t < kW; ++t) {
+        const int i = i0 + t < K ? i0 + t : K - 1;
+        was |= (unsigned)prev[(size_t)i * Bp] << t;
+    }
+    const int nv = K - i0;   // the window's positions below K
+    return was & (nv >= kW ? (1u << kW) - 1 : nv > 0 ? (1u << nv) - 1 : 0u);
+}
+
+// SISO `DEC` of iteration `it` over the positions [g.start, g.end) of codeword b (Max-Log-MAP, or log-MAP
+// with mx a MaxStar), with everything that follows it in the iteration: the extrinsic (ext12 / ext21 and
+// the caller's Le), and after SISO2 the hard decisions.  A recursion that starts at the trellis' end starts
+// from the terminated state, any other from equal metrics (all 0: never normalised, so the sums stay inside
+// the bounds at the head of this file).  The warm-ups take any start: sixteen steps at a time with their
+// loads ahead of the arithmetic, then the rest one by one.  The span's own steps: alpha checkpoints at
+// ckpt[w], w the window's index in the whole trellis (sub-blocks own disjoint slots), then per window,
+// backwards, alpha again from its checkpoint, beta, Lambda, f and the stores.  g must be the same in every
+// lane of a wave.  Sub-blocks of one SISO read ext / xs / xp anywhere and write only their own positions of
+// the other ext array, so they may run in any order or at once; the next SISO may start when all of them
+// are done.
 //
-// STOP (td_set_fixed_window_stop, sp its rule): the caller runs only the lanes whose codeword has not
-// stopped.  SISO2 writes row `it` of bitsT in every iteration, by interleaved position as siso_pass<1, true>
-// does, and in a judged iteration (it + 1 >= sp->first) stores the rule's evidence on the sub-block's
-// own positions below K at ev[sb][b]: HDA the bits that differ from row it - 1 (OR over the windows),
-// CRC the XOR of syn[i] over the 1 bits.  HDA's previous bits are not read back from bitsT: sixteen
-// byte loads a window cost this schedule, which keeps the chip full, 16-20 % of the decode where nothing
-// converges.  A lane leaves the sixteen bits of each of its 16-step windows packed at hist[w][b] (w the
-// window's index in the whole trellis, as for ckpt) when the next iteration is judged, and the window's
-// previous bits are one 16-bit load together with the window's inputs; the slot is the lane's own, read
-// before it is written.  The codeword's evidence is the fold of its sub-blocks' words, which the launch
-// after SISO2's makes (fx_window_judge_kernel): no atomics, and no launch reads a word of ev that it writes.
+// STOP (the stopping decoders, sp their rule; the caller runs only the lanes whose codeword has not
+// stopped): SISO2 writes row `it` of bitsT in every iteration, and in a judged iteration
+// (it + 1 >= sp->first) makes the rule's evidence on the span's own positions below K, zero where the
+// codeword may stop: HDA the bits that differ from row it - 1 (OR over the windows), CRC the XOR of
+// syn[i] over the 1 bits.  Both rules hold in any fixed order of the bits, so the stopping decoders keep
+// bitsT in SISO2's own order, by interleaved position i: the stores and the rule need no entry of pi (a
+// scalar load and its wait in every step otherwise), and the transpose back undoes the order
+// (fx_bits_stop_kernel reads row pinv[k]).  The window's new bits are packed one bit a step into a
+// register and compared with its previous bits at its end; the state is the evidence and two bit masks.
+// SUB chooses where the previous bits come from and where the evidence goes:
+//   the exact schedule (SUB false) loads the window's sixteen bytes of row it - 1 with the window's inputs
+//     (row_bits) -- sixteen loads in flight ahead of the arithmetic, not one per step behind a store that
+//     the compiler must assume aliases it; the previous row stays in the workspace.  It packs the new bits
+//     only in a judged iteration and returns the evidence to decode_codeword_stop.
+//   the sub-block schedule (SUB true) does not read them back from bitsT: sixteen byte loads a window cost
+//     this schedule, which keeps the chip full, 16-20 % of the decode where nothing converges.  A lane
+//     leaves the sixteen bits of each of its 16-step windows packed at hist[w][b] (w the window's index in
+//     the whole trellis, as for ckpt) when the next iteration is judged, and the window's previous bits are
+//     one 16-bit load together with the window's inputs; the slot is the lane's own, read before it is
+//     written.  It packs the new bits whenever the rule is HDA and stores the evidence at ev[sb][b]: the
+//     codeword's is the fold of its sub-blocks' words, which the launch after SISO2's makes
+//     (fx_window_judge_kernel): no atomics, and no launch reads a word of ev that it writes.
 //
 // NII (td_set_fixed_window_nii, ni its state): in iterations after the first a warm-up that does not start at
 // a trellis end loads its start vector from the sub-block's own slot, and the sub-block stores the vectors
@@ -417,94 +367,67 @@ TDF_HD void nii_load(const uint32_t* slot, size_t Bp, size_t b, int (&v)[8])
 //                      past (sb + 1) W, also B[(sb + 1) W + r], the start of sub-block sb - q;
 // bt after the backward loop's window that begins there.  The last sub-block holds no A, as nothing starts
 // to its right.  Every slot that is loaded was stored by the launch of this SISO one iteration earlier.
-template <int DEC, bool STOP, bool NII = false, class M = MaxLog>
-TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop* sp, uint32_t* ev, uint16_t* hist,
-                               const FxNii* ni, size_t b, int it, int sb, const M& mx = M())
+template <int DEC, bool STOP, bool NII, bool SUB, class M>
+TDF_HD int siso_span(const FxArgs& p, const FxSpan g, const FxStop* sp, uint32_t* ev, uint16_t* hist, const FxNii* ni,
+                     size_t b, int it, const M& mx)
 {
-    const int L = p.L, K = p.K, W = wn.window;
-    const int nS = window_blocks(L, W);
-    const bool live = b < (size_t)p.B;
-    const int start = sb * W, end = sb == nS - 1 ? L : start + W;
-    const bool a_term = start - wn.overlap <= 0, b_term = end + wn.overlap >= L;
-    const int a_from = a_term ? 0 : start - wn.overlap, b_from = b_term ? L : end + wn.overlap;
-    const int w0 = start / kW, w1 = (end + kW - 1) / kW;   // the sub-block's recomputation windows
+    const int L = p.L, K = p.K;
+    const bool live = b < (size_t)p.B;   // a lane of the padding decodes zeros and stores nothing outside the workspace
+    const int start = g.start, end = g.end, sb = g.sb, nS = g.nS;
+    const bool a_term = g.a_from == 0, b_term = g.b_from == L;
+    const int w0 = start / kW, w1 = (end + kW - 1) / kW;   // the span's recomputation windows
     // NII: the positions whose vectors this sub-block stores (-1: none) and the consumers' slots
     int a_st = -1, a_slot = 0, b_st0 = -1, b_st1 = -1, b_slot = 0;
     if (NII && it + 1 < p.iters) {
         a_slot = sb + 1 + ni->q;
-        if (a_slot <= nS - 1) a_st = start + W - ni->r;
+        if (a_slot <= nS - 1) a_st = start + g.W - ni->r;
         b_slot = sb - 1 - ni->q;
         if (b_slot >= 0) b_st0 = start + ni->r;
-        if (sb == nS - 1 && ni->q >= 1 && b_slot + 1 >= 0 && start + W + ni->r < L) b_st1 = start + W + ni->r;
+        if (sb == nS - 1 && ni->q >= 1 && b_slot + 1 >= 0 && start + g.W + ni->r < L) b_st1 = start + g.W + ni->r;
     }
 
+    // forward: the warm-up, then alpha at every window start
     {
         int a[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) a[s] = s && a_term ? kNeg : 0;
         if (NII && it > 0 && !a_term) nii_load(ni->rd + (size_t)sb * 4 * p.Bp, p.Bp, b, a);
-        int i = a_from;
-        for (; i + kW <= start; i += kW) {
-            int S[kW], P[kW];
-#pragma unroll
-            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i + t, S[t], P[t]);
-#pragma unroll
-            for (int t = 0; t < kW; ++t) {
-                int n[8];
-                alpha_step(a, S[t], P[t], n, mx);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) a[s] = n[s];
-            }
-        }
+        int i = g.a_from;
+        for (; i + kW <= start; i += kW) alpha_block<DEC>(p, b, it, i, a, mx);
         for (; i < start; ++i) {
             int S, P, n[8];
             load_step<DEC>(p, b, it, i, S, P);
             alpha_step(a, S, P, n, mx);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) a[s] = n[s];
+            copy8(a, n);
         }
         for (int w = w0; w < w1; ++w) {
 #pragma unroll
             for (int s = 0; s < 8; ++s) p.ckpt[((size_t)w * 8 + s) * p.Bp + b] = a[s];
             if (NII && w * kW == a_st) nii_store(ni->wr + (size_t)a_slot * 4 * p.Bp, p.Bp, b, a);
-            if (w == w1 - 1) break;   // a window that is not the sub-block's last is whole
-            int S[kW], P[kW];
-#pragma unroll
-            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, w * kW + t, S[t], P[t]);
-#pragma unroll
-            for (int t = 0; t < kW; ++t) {
-                int n[8];
-                alpha_step(a, S[t], P[t], n, mx);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) a[s] = n[s];
-            }
+            if (w == w1 - 1) break;   // a window that is not the span's last is whole
+            alpha_block<DEC>(p, b, it, w * kW, a, mx);
         }
     }
 
+    // backward: the warm-up, then per window alpha again from its checkpoint, beta and the outputs
     int bt[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) bt[s] = s && b_term ? kNeg : 0;
     if (NII && it > 0 && !b_term) nii_load(ni->rd + (size_t)(nS + sb) * 4 * p.Bp, p.Bp, b, bt);
     {
-        int i = b_from;
-        for (; i - kW >= end; i -= kW) {
-            int S[kW], P[kW];
-#pragma unroll
-            for (int t = 0; t < kW; ++t) load_step<DEC>(p, b, it, i - 1 - t, S[t], P[t]);
-#pragma unroll
-            for (int t = 0; t < kW; ++t) beta_step(bt, S[t], P[t], mx);
-        }
+        int i = g.b_from;
+        for (; i - kW >= end; i -= kW) beta_block<DEC>(p, b, it, i, bt, mx);
         for (; i > end; --i) {
             int S, P;
             load_step<DEC>(p, b, it, i - 1, S, P);
             beta_step(bt, S, P, mx);
         }
     }
-
     const int row = STOP || p.all_iters ? it : 0;
     const bool want_bits = DEC == 1 && (STOP || p.all_iters || it == p.iters - 1);
-    const bool judge = STOP && DEC == 1 && it + 1 >= sp->first;
+    const bool judge = STOP && DEC == 1 && it + 1 >= sp->first;   // iterations before sp->first are not judged
     const bool hda = STOP && DEC == 1 && sp->rule == 1;
+    const bool pack = SUB ? hda : hda && judge;
     int acc = 0;
     for (int w = w1 - 1; w >= w0; --w) {
         const int i0 = w * kW;
@@ -515,7 +438,8 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
             load_step<DEC>(p, b, it, i, S[t], P[t]);
         }
         unsigned was = 0, now = 0;   // HDA: bit t = the bit of position i0 + t in row it - 1, in row it
-        if (STOP && judge && hda) was = hist[(size_t)w * p.Bp + b];   // first >= 2: the window's word of row it - 1
+        if (STOP && judge && hda)    // first >= 2: row it - 1 exists
+            was = SUB ? hist[(size_t)w * p.Bp + b] : row_bits(p.bitsT + (size_t)(row - 1) * K * p.Bp + b, p.Bp, K, i0);
         int A[kW][8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) A[0][s] = p.ckpt[((size_t)w * 8 + s) * p.Bp + b];
@@ -554,9 +478,9 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
                 } else if (want_bits && i < K) {
                     const int bit = llr < 0 ? 0 : 1;
                     p.bitsT[((size_t)row * K + (size_t)i) * p.Bp + b] = (uint8_t)bit;
-                    if (hda)
+                    if (pack)
                         now |= (unsigned)bit << t;
-                    else if (judge)
+                    else if (judge && !hda)   // CRC: the syndrome of every 1 bit, from a table in the same order
                         acc ^= -bit & table_entry(sp->syn, i);
                 }
 #pragma unroll
@@ -565,26 +489,31 @@ TDF_HD void siso_window_pass_t(const FxArgs& p, const FxWindow& wn, const FxStop
         }
         if (STOP && hda) {
             if (judge) acc |= (int)(was ^ now);
-            if (it + 2 >= sp->first && it + 1 < p.iters)   // there is a next iteration, and it is judged
+            if (SUB && it + 2 >= sp->first && it + 1 < p.iters)   // there is a next iteration, and it is judged
                 hist[(size_t)w * p.Bp + b] = (uint16_t)now;
         }
         if (NII && (i0 == b_st0 || i0 == b_st1))
             nii_store(ni->wr + (size_t)(nS + (i0 == b_st0 ? b_slot : b_slot + 1)) * 4 * p.Bp, p.Bp, b, bt);
     }
-    if (STOP && judge) ev[(size_t)sb * p.Bp + b] = (uint32_t)acc;
+    if (SUB && STOP && judge) ev[(size_t)sb * p.Bp + b] = (uint32_t)acc;
+    return acc;
 }
 
-template <int DEC, class M = MaxLog>
-TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb, const M& mx = M())
+// The exact schedule's pass: one terminated span over the whole trellis.  With STOP it returns the rule's
+// evidence on row `it`, zero where the codeword may stop.
+template <int DEC, bool STOP, class M = MaxLog>
+TDF_HD int siso_pass(const FxArgs& p, const FxStop* sp, size_t b, int it, const M& mx = M())
 {
-    siso_window_pass_t<DEC, false>(p, wn, nullptr, nullptr, nullptr, nullptr, b, it, sb, mx);
+    return siso_span<DEC, STOP, false, false>(p, FxSpan{0, p.L, 0, p.L, 0, 1, p.L}, sp, nullptr, nullptr, nullptr, b, it, mx);
 }
 
-template <int DEC, class M = MaxLog>
-TDF_HD void siso_window_pass_nii(const FxArgs& p, const FxWindow& wn, const FxNii& ni, size_t b, int it, int sb,
-                                 const M& mx = M())
+template <class M = MaxLog>
+TDF_HD void decode_codeword(const FxArgs& p, size_t b, const M& mx = M())
 {
-    siso_window_pass_t<DEC, false, true>(p, wn, nullptr, nullptr, nullptr, &ni, b, it, sb, mx);
+    for (int it = 0; it < p.iters; ++it) {
+        siso_pass<0, false>(p, nullptr, b, it, mx);
+        siso_pass<1, false>(p, nullptr, b, it, mx);
+    }
 }
 
 // true if `run` holds in any lane of the wave (on the host: for the one codeword of the call)
@@ -622,28 +551,45 @@ TDF_HD void decode_codeword_stop(const FxArgs& p, const FxStop& s, size_t b, con
     s.used[b] = used;
 }
 
-// One lane of the stopping sub-block kernels: SISO `DEC` of iteration `it`, sub-block sb of codeword b.
-// s.used is the state that the decode resets to 0 at its start: 0 = running, n = stopped after n
+// One lane of the sub-block kernels: SISO `DEC` of iteration `it`, sub-block sb of codeword b, the span of
+// window_span.  sb must be the same in every lane of a wave.  Without STOP s, ev and hist are not read, and
+// without NII ni is not.
+// STOP: s.used is the state that the decode resets to 0 at its start: 0 = running, n = stopped after n
 // iterations.  A wave none of whose lanes runs returns on the ballot -- where the time is saved -- and a
 // stopped lane of a running wave is skipped by a branch and writes nothing; a lane of the padding never
-// runs.  sb must be the same in every lane of a wave.
+// runs.  With NII too: a codeword that runs in iteration `it` ran in it - 1, so its slots hold its own vectors.
+template <int DEC, bool STOP, bool NII, class M>
+TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist,
+                             const FxNii& ni, size_t b, int it, int sb, const M& mx)
+{
+    if (STOP) {
+        const bool run = b < (size_t)p.B && s.used[b] == 0;
+        if (!any_lane(run) || !run) return;
+    }
+    siso_span<DEC, STOP, NII, true>(p, window_span(p.L, wn, sb), &s, ev, hist, &ni, b, it, mx);
+}
+
+// The entry with one setting's arguments alone -- none, NII, a rule -- for a caller that knows its setting when
+// it is written: the host program of the tests, a lane at a time.  The kernels take all arguments and use the
+// entry above.
+template <int DEC, class M = MaxLog>
+TDF_HD void siso_window_pass(const FxArgs& p, const FxWindow& wn, size_t b, int it, int sb, const M& mx = M())
+{
+    siso_window_pass<DEC, false, false>(p, wn, FxStop{}, nullptr, nullptr, FxNii{}, b, it, sb, mx);
+}
+
+template <int DEC, class M = MaxLog>
+TDF_HD void siso_window_pass_nii(const FxArgs& p, const FxWindow& wn, const FxNii& ni, size_t b, int it, int sb,
+                                 const M& mx = M())
+{
+    siso_window_pass<DEC, false, true>(p, wn, FxStop{}, nullptr, nullptr, ni, b, it, sb, mx);
+}
+
 template <int DEC, class M = MaxLog>
 TDF_HD void siso_window_stop(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist, size_t b,
                              int it, int sb, const M& mx = M())
 {
-    const bool run = b < (size_t)p.B && s.used[b] == 0;
-    if (!any_lane(run)) return;
-    if (run) siso_window_pass_t<DEC, true>(p, wn, &s, ev, hist, nullptr, b, it, sb, mx);
-}
-
-// The same with NII: a codeword that runs in iteration `it` ran in it - 1, so its slots hold its own vectors.
-template <int DEC, class M = MaxLog>
-TDF_HD void siso_window_stop_nii(const FxArgs& p, const FxWindow& wn, const FxStop& s, uint32_t* ev, uint16_t* hist,
-                                 const FxNii& ni, size_t b, int it, int sb, const M& mx = M())
-{
-    const bool run = b < (size_t)p.B && s.used[b] == 0;
-    if (!any_lane(run)) return;
-    if (run) siso_window_pass_t<DEC, true, true>(p, wn, &s, ev, hist, &ni, b, it, sb, mx);
+    siso_window_pass<DEC, true, false>(p, wn, s, ev, hist, FxNii{}, b, it, sb, mx);
 }
 
 // The decision after SISO2's launch of iteration `it`, one call per codeword: a running codeword stops
