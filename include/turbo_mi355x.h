@@ -542,6 +542,23 @@ int td_modulate(const uint8_t* d_bits, long long nsym, int modulation, double* d
 int td_demodulate(const double* d_yi, const double* d_yq, long long nsym, int modulation, double Kf, double* d_llr,
                   void* stream);
 
+/*
+ * d_in [n] double -> d_out [n] in `precision` (enum td_precision): the conversion between td_demodulate's
+ * output and what td_rate_dematch and td_decode_device take (an extension: the reference decodes doubles only).
+ * No handle.
+ *   TD_F64    a copy.
+ *   TD_F32    (float)x, the IEEE round-to-nearest-even narrowing; a value too large becomes +-inf.
+ *   TD_FIXED  the int8 q = clamp(rint(x * steps_per_unit), -127, 127): the product is one rounded double
+ *             multiply, rint rounds to nearest with ties to even, and the clamp happens in double before the
+ *             conversion to integer, so +-1e300 and +-inf give +-127 and no conversion is undefined.  -128 is
+ *             never produced.
+ * NaN inputs: unspecified (the library is built with -fno-honor-nans).  steps_per_unit is used only with
+ * TD_FIXED.  Asynchronous on `stream`, allocates nothing, may be captured into a hipGraph.  n = 0 is a no-op.
+ * Pointers need only element alignment; the bytes do not depend on it.
+ * TD_EINVAL: a null pointer, n < 0, an unknown precision, with TD_FIXED steps_per_unit not finite or <= 0.
+ */
+int td_llr_convert(const double* d_in, long long n, int precision, double steps_per_unit, void* d_out, void* stream);
+
 /* Error counts per frame and iteration for the BER harness (main.cpp:224-237):
  * d_err[b][it] = #{i < K : d_bits[b][it][i] != d_info[b][i]}, d_bits as td_decode_device's
  * all_iters output with `iters` rows. */
@@ -581,6 +598,27 @@ int td_rate_match(td_handle* h, const void* d_in, int elem_size, int B, int rv, 
  * from d_llr itself (-128 read as -127) with `accumulate` and from 0 without; a position no k selects
  * keeps its value (accumulate) or is 0. */
 int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d_llr, int accumulate, void* stream);
+/*
+ * The receive front end in one pass: received symbols -> the handle's soft buffer, with no LLR array in
+ * between.  d_yi, d_yq [B][E / modulation] double symbols, codeword b's own E / modulation of them.  By
+ * definition, byte for byte:
+ *   demap    transmitted value k of codeword b is element b E + k of what td_demodulate(d_yi, d_yq,
+ *            B E / modulation, modulation, Kf, .) writes: bit k % modulation of symbol
+ *            b (E / modulation) + k / modulation;
+ *   convert  that value goes through td_llr_convert to the handle's precision (steps_per_unit is used only on
+ *            a TD_FIXED handle and ignored otherwise);
+ *   combine  d_llr [B][3K+12] is what td_rate_dematch(h, e, B, rv, E, d_llr, accumulate, stream) gives on
+ *            those e: sums in ascending k in the buffer's precision, int8 saturated to +-127 after every
+ *            addition with -128 in the prior buffer read as -127, unselected positions kept (accumulate) or
+ *            zero, no atomics, the same bytes on every run.
+ * It uses the tables of td_rm_set, allocates nothing and may be captured into a hipGraph.  Asynchronous on
+ * `stream`.  B = 0 is a no-op.  NaN symbols: unspecified, as for td_llr_convert.
+ * TD_EINVAL: everything td_rate_dematch rejects (a null pointer, rv outside 0..3, E < 1, B < 0, a handle
+ * without tables), modulation not 1, 2, 3, 4 or 6, E not a multiple of modulation (LTE's E always is one),
+ * a TD_FIXED handle with steps_per_unit not finite or <= 0.
+ */
+int td_demod_dematch(td_handle* h, const double* d_yi, const double* d_yq, int B, int rv, int E, int modulation,
+                     double Kf, double steps_per_unit, void* d_llr, int accumulate, void* stream);
 /* Host only (no GPU, no handle): idx[k] = the stream position of e_k, k < E.  1 <= K <= 10000. */
 int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx);
 
@@ -588,8 +626,8 @@ int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx);
  * The transmit side on device-resident bits (an extension: the reference encodes one frame per call on the
  * host, TurboEnCoding, log_map.cpp:530-583, which the compat layer keeps).  With these the chain closes on
  * the GPU: td_crc_attach -> td_encode_device -> td_rate_match -> td_modulate -> (the caller's channel) ->
- * td_demodulate -> td_rate_dematch -> td_decode_device.  They work on a handle of any precision and use
- * only its K, f1, f2, device and QPP table.
+ * td_demod_dematch (= td_demodulate -> td_llr_convert -> td_rate_dematch) -> td_decode_device.  They work
+ * on a handle of any precision and use only its K, f1, f2, device and QPP table.
  *
  * td_encode_device: d_info [B][K] uint8 (any non-zero byte is a 1, as td_crc24_host reads them) ->
  * d_coded [B][3K+12] uint8, each 0 or 1, in the stream layout of encoderm_turbo (log_map.cpp:566-578):

@@ -33,6 +33,7 @@ EXPORTS = (
     "td_set_fixed", "td_set_fixed_stop", "td_set_fixed_window", "td_set_fixed_window_stop",
     "td_set_fixed_maxstar", "td_fixed_maxstar_table", "td_set_fixed_window_nii", "td_debug_workspace_fill",
     "td_encode_device", "td_crc_set", "td_crc_attach", "td_crc_check",
+    "td_llr_convert", "td_demod_dematch",
 )
 
 
@@ -153,6 +154,9 @@ def lib() -> C.CDLL:
         L.td_crc_set.argtypes = [P, C.c_uint32]
         L.td_crc_attach.argtypes = [P, P, I, P]
         L.td_crc_check.argtypes = [P, P, I, P, P]
+    if hasattr(L, "td_llr_convert"):   # the receive front end (older A/B builds loaded by TD_LIB_PATH lack it)
+        L.td_llr_convert.argtypes = [P, C.c_longlong, I, C.c_double, P, P]
+        L.td_demod_dematch.argtypes = [P, P, P, I, I, I, I, C.c_double, C.c_double, P, I, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

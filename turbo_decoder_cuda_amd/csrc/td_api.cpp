@@ -1668,6 +1668,32 @@ int td_demodulate(const double* d_yi, const double* d_yq, long long nsym, int mo
     return TD_OK;
 }
 
+namespace {
+
+// steps_per_unit finite and > 0, judged on its bits: the library is built with -fno-honor-nans, under which
+// a floating-point comparison may let a NaN through
+bool steps_ok(double s)
+{
+    uint64_t u;
+    std::memcpy(&u, &s, sizeof u);
+    return (u >> 63) == 0 && ((u >> 52) & 0x7FF) != 0x7FF && (u << 1) != 0;
+}
+
+}  // namespace
+
+int td_llr_convert(const double* d_in, long long n, int precision, double steps_per_unit, void* d_out, void* stream)
+{
+    if (!d_in || !d_out) return fail(TD_EINVAL, "td_llr_convert: null pointer");
+    if (n < 0) return fail(TD_EINVAL, "td_llr_convert: negative n");
+    if (precision != TD_F64 && precision != TD_F32 && precision != TD_FIXED)
+        return fail(TD_EINVAL, "td_llr_convert: precision must be TD_F64, TD_F32 or TD_FIXED");
+    if (precision == TD_FIXED && !steps_ok(steps_per_unit))
+        return fail(TD_EINVAL, "td_llr_convert: steps_per_unit must be finite and positive");
+    if (n == 0) return TD_OK;
+    TD_HIP(td::launch_llr_convert(d_in, n, precision, steps_per_unit, d_out, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
 int td_count_errors(td_handle* h, const uint8_t* d_bits, int iters, const uint8_t* d_info, int B, int* d_err,
                     void* stream)
 {
@@ -1758,6 +1784,32 @@ int td_rate_dematch(td_handle* h, const void* d_e, int B, int rv, int E, void* d
         TD_HIP(td::launch_rate_dematch<double>(p, static_cast<const double*>(d_e), static_cast<double*>(d_llr), accumulate, st));
     else
         TD_HIP(td::launch_rate_dematch<float>(p, static_cast<const float*>(d_e), static_cast<float*>(d_llr), accumulate, st));
+    return TD_OK;
+}
+
+int td_demod_dematch(td_handle* h, const double* d_yi, const double* d_yq, int B, int rv, int E, int modulation,
+                     double Kf, double steps_per_unit, void* d_llr, int accumulate, void* stream)
+{
+    td::RmParams p;
+    if (const int rc = rm_launch_params("td_demod_dematch", h, d_yi, d_llr, B, rv, E, p)) return rc;
+    if (!d_yq) return fail(TD_EINVAL, "td_demod_dematch: null argument");
+    const int M = modulation;
+    if (M != 1 && M != 2 && M != 3 && M != 4 && M != 6)
+        return fail(TD_EINVAL, "td_demod_dematch: modulation must be 1, 2, 3, 4 or 6");
+    if (E % M) return fail(TD_EINVAL, "td_demod_dematch: E = " + std::to_string(E) + " is not a whole number of symbols");
+    if (is_fixed(h) && !steps_ok(steps_per_unit))
+        return fail(TD_EINVAL, "td_demod_dematch: steps_per_unit must be finite and positive");
+    if (B == 0) return TD_OK;
+    if (!td::launch_demod_dematch<double> || !td::launch_demod_dematch<float> || !td::launch_demod_dematch<int8_t>)
+        return fail(TD_EHIP, "td_demod_dematch: this build has no td_ratematch.hip");
+    TD_HIP(hipSetDevice(h->p.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (is_fixed(h))
+        TD_HIP(td::launch_demod_dematch<int8_t>(p, d_yi, d_yq, M, Kf, steps_per_unit, static_cast<int8_t*>(d_llr), accumulate, st));
+    else if (h->p.precision == TD_F64)
+        TD_HIP(td::launch_demod_dematch<double>(p, d_yi, d_yq, M, Kf, steps_per_unit, static_cast<double*>(d_llr), accumulate, st));
+    else
+        TD_HIP(td::launch_demod_dematch<float>(p, d_yi, d_yq, M, Kf, steps_per_unit, static_cast<float*>(d_llr), accumulate, st));
     return TD_OK;
 }
 

@@ -170,6 +170,9 @@ hipError_t launch_synth(const SynthParams& p, hipStream_t st);
 hipError_t launch_modulate(const uint8_t* bits, long long nsym, int M, double* si, double* sq, hipStream_t st);
 hipError_t launch_demodulate(const double* yi, const double* yq, long long nsym, int M, double Kf, double* out,
                              hipStream_t st);
+// td_llr_convert: d_in [n] double -> d_out [n] in `precision` (enum td_precision; else hipErrorInvalidValue)
+hipError_t launch_llr_convert(const double* d_in, long long n, int precision, double steps_per_unit, void* d_out,
+                              hipStream_t st);
 hipError_t launch_count_errors(const uint8_t* bits, const uint8_t* info, int K, int iters, int B, int* err,
                                hipStream_t st);
 

@@ -86,5 +86,13 @@ __attribute__((weak)) hipError_t launch_rate_match(const RmParams& p, const void
 template <typename T>
 __attribute__((weak)) hipError_t launch_rate_dematch(const RmParams& p, const T* d_e, T* d_out, int accumulate,
                                                      hipStream_t st);
+// td_demod_dematch: d_yi, d_yq [B][E / M] symbols -> d_out [B][3K+12], the values demapped (M = 1, 2, 3, 4, 6
+// bits per symbol; else hipErrorInvalidValue) and converted to T where launch_rate_dematch reads d_e.  T =
+// double, float, or int8_t (a TD_FIXED handle: quantised at steps_per_unit, every addition saturated to +-127,
+// the bytes of launch_fixed_dematch on the quantised values).  p.E is a multiple of M.
+template <typename T>
+__attribute__((weak)) hipError_t launch_demod_dematch(const RmParams& p, const double* d_yi, const double* d_yq, int M,
+                                                      double Kf, double steps_per_unit, T* d_out, int accumulate,
+                                                      hipStream_t st);
 
 }  // namespace td

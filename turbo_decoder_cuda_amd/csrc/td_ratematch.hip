@@ -1,8 +1,10 @@
 // td_ratematch.hip -- LTE rate matching (36.212 5.1.4.1) on the device: the transmit-side bit
 // selection (rate_match_kernel, a gather) and the receive-side soft de-rate-matching with repetition
-// combining and HARQ accumulation (rate_dematch_kernel).  Tables and notation: td_ratematch.h.
+// combining and HARQ accumulation (rate_dematch_kernel), also fused behind the demapper and the LLR conversion
+// (demod_dematch_kernel: td_demod_dematch, symbols in, soft buffer out).  Tables and notation: td_ratematch.h.
 #include <hip/hip_runtime.h>
 
+#include "td_demap_core.h"
 #include "td_ratematch.h"
 
 namespace td {
@@ -23,6 +25,19 @@ __global__ __launch_bounds__(kRmThreads) void rate_match_kernel(RmParams p, cons
     for (size_t b = blockIdx.y; b < (size_t)p.B; b += gridDim.y) e[b * (size_t)p.E + k] = in[b * n + src];
 }
 
+// One addition of a position's sum: in the buffer's precision; int8 (td_demod_dematch on a TD_FIXED handle)
+// saturates to +-127 and reads a prior -128 as -127.  A position nothing selects is never added to.
+template <typename T>
+__device__ __forceinline__ T sum_add(T acc, T v)
+{
+    return acc + v;
+}
+__device__ __forceinline__ int8_t sum_add(int8_t acc, int8_t v)
+{
+    const int a = (acc < -127 ? -127 : acc) + v;
+    return (int8_t)(a > 127 ? 127 : a < -127 ? -127 : a);
+}
+
 // De-rate-matching.  Stream position q = 3k+i sits in row (ND+k) / 32, column (ND+k) % 32 of its
 // stream's 32-column matrix, and the buffer reads that matrix column by column: consecutive q are
 // consecutive columns, R elements apart in e (2R in the parity part).  One thread per q in stream
@@ -37,13 +52,21 @@ __global__ __launch_bounds__(kRmThreads) void rate_match_kernel(RmParams p, cons
 // (row pitch 97: the lanes of a run are one row apart, 96 would put them all on one bank), and after a
 // barrier the band leaves in stream order: every wave stores one contiguous piece of d_llr.
 //
-// All accesses are one element wide (8 or 4 bytes), so rows of e or d_llr that are only
+// All accesses are one element wide (8, 4 or 1 bytes), so rows of e or d_llr that are only
 // element-aligned (odd E or odd K with B > 1) take the same path as aligned ones.
 //
 // The sum of a position is formed by its one owning thread, in ascending k, starting from the prior
 // value (accumulate) or +0.0: no atomics, the same bits on every run.
-template <typename T, bool ACC, int kRows>
-__global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, const T* __restrict__ e, T* out)
+//
+// Where e comes from is the body's one parameter: src.row(b)[k] is e[b][k] -- td_rate_dematch's array
+// (rate_dematch_kernel), or td_demod_dematch's symbols, demapped and converted where the array would be
+// read (demod_dematch_kernel; td_demap_core.h).  There a run of consecutive k is a run of consecutive
+// symbols, M values each, so a wave's loads of symbols are as contiguous as its loads of e are.  The int8
+// front end (a TD_FIXED handle) takes this layout too, with sum_add's saturating addition: one thread per
+// stream position, td_rate_dematch's own int8 kernel (td_fixed.hip), has every lane fetch a 16-byte symbol
+// from a line of its own and measured 2.9 - 6.1 x slower at B = 32768 (DESIGN.md "Receive front end").
+template <typename T, bool ACC, int kRows, typename Src>
+__device__ __forceinline__ void dematch_band(const RmParams& p, const Src& src, T* out)
 {
     constexpr int kTile = 96 * kRows, kPitch = 97, kPer = kTile / kRmThreads;
     static_assert(kTile % kRmThreads == 0, "whole passes over the band");
@@ -79,7 +102,7 @@ __global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, co
     int it = 0;
     for (size_t b = blockIdx.y; b < (size_t)p.B; b += gridDim.y, ++it) {
         T* buf = tile[it & 1];   // two tiles: one barrier separates a codeword's stores from the next one's sums
-        const T* eb = e + b * (size_t)p.E;
+        const auto eb = src.row(b);
         T* ob = out + b * (size_t)nout;
         if constexpr (ACC) {
 #pragma unroll
@@ -99,8 +122,8 @@ __global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, co
             T acc = T(0);
             if constexpr (ACC) acc = buf[slot[n]];
             if (first[n] >= 0 && first[n] < p.E) {
-                acc += v[n];
-                for (size_t k = (size_t)first[n] + (size_t)p.Nnn; k < (size_t)p.E; k += (size_t)p.Nnn) acc += eb[k];
+                acc = sum_add(acc, v[n]);
+                for (size_t k = (size_t)first[n] + (size_t)p.Nnn; k < (size_t)p.E; k += (size_t)p.Nnn) acc = sum_add(acc, eb[k]);
             }
             buf[slot[n]] = acc;
         }
@@ -111,6 +134,21 @@ __global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, co
             if (q >= 0 && q < nout) ob[q] = buf[(x / 96) * kPitch + x % 96];
         }
     }
+}
+
+template <typename T, bool ACC, int kRows>
+__global__ __launch_bounds__(kRmThreads) void rate_dematch_kernel(RmParams p, const T* __restrict__ e, T* out)
+{
+    dematch_band<T, ACC, kRows>(p, ArraySrc<T>{e, (size_t)p.E}, out);
+}
+
+// td_demod_dematch: d_yi, d_yq [B][E / M] -> out [B][3K+12] in one pass; T = double, float or int8_t
+template <int M, typename T, bool ACC, int kRows>
+__global__ __launch_bounds__(kRmThreads) void demod_dematch_kernel(RmParams p, const double* __restrict__ yi,
+                                                                    const double* __restrict__ yq, double Kf,
+                                                                    double steps_per_unit, T* out)
+{
+    dematch_band<T, ACC, kRows>(p, DemapSrc<M, T>{yi, yq, (size_t)(p.E / M), Kf, steps_per_unit}, out);
 }
 
 constexpr int kRmRows = 16;
@@ -150,6 +188,41 @@ hipError_t launch_rate_dematch(const RmParams& p, const T* d_e, T* d_out, int ac
     return hipGetLastError();
 }
 
+template <int M, typename T>
+static hipError_t launch_demod_dematch_m(const RmParams& p, const double* yi, const double* yq, double Kf,
+                                         double steps_per_unit, T* d_out, int accumulate, hipStream_t st)
+{
+    // td_rate_dematch's grid, cap included (crossed by tests/test_gpu_frontend.py test_demod_dematch_past_the_grid_cap)
+    const dim3 grid((unsigned)((p.R + kRmRows - 1) / kRmRows), (unsigned)p.B < kRmGridY ? (unsigned)p.B : kRmGridY);
+    if (accumulate)
+        hipLaunchKernelGGL((demod_dematch_kernel<M, T, true, kRmRows>), grid, dim3(kRmThreads), 0, st, p, yi, yq, Kf, steps_per_unit,
+                           d_out);
+    else
+        hipLaunchKernelGGL((demod_dematch_kernel<M, T, false, kRmRows>), grid, dim3(kRmThreads), 0, st, p, yi, yq, Kf, steps_per_unit,
+                           d_out);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_demod_dematch(const RmParams& p, const double* d_yi, const double* d_yq, int M, double Kf,
+                                double steps_per_unit, T* d_out, int accumulate, hipStream_t st)
+{
+    switch (M) {
+        case 1: return launch_demod_dematch_m<1>(p, d_yi, d_yq, Kf, steps_per_unit, d_out, accumulate, st);
+        case 2: return launch_demod_dematch_m<2>(p, d_yi, d_yq, Kf, steps_per_unit, d_out, accumulate, st);
+        case 3: return launch_demod_dematch_m<3>(p, d_yi, d_yq, Kf, steps_per_unit, d_out, accumulate, st);
+        case 4: return launch_demod_dematch_m<4>(p, d_yi, d_yq, Kf, steps_per_unit, d_out, accumulate, st);
+        case 6: return launch_demod_dematch_m<6>(p, d_yi, d_yq, Kf, steps_per_unit, d_out, accumulate, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template hipError_t launch_demod_dematch<double>(const RmParams&, const double*, const double*, int, double, double,
+                                                 double*, int, hipStream_t);
+template hipError_t launch_demod_dematch<float>(const RmParams&, const double*, const double*, int, double, double, float*,
+                                                int, hipStream_t);
+template hipError_t launch_demod_dematch<int8_t>(const RmParams&, const double*, const double*, int, double, double,
+                                                 int8_t*, int, hipStream_t);
 template hipError_t launch_rate_dematch<double>(const RmParams&, const double*, double*, int, hipStream_t);
 template hipError_t launch_rate_dematch<float>(const RmParams&, const float*, float*, int, hipStream_t);
 

@@ -413,6 +413,39 @@ class TurboCodec:
                                         int(bool(accumulate)), C.c_void_p(stream.cuda_stream)))
         return out
 
+    def demod_dematch(self, yi, yq, rv: int, E: int, modulation: int, Kf: float, steps_per_unit: float = 8.0,
+                      out=None, accumulate: bool = False, stream=None):
+        """The receive front end in one pass (td_demod_dematch): yi, yq float64 [B, E / modulation], the
+        received symbols of a transmission of redundancy version rv -> LLRs [B, 3K+12] in the codec's dtype,
+        byte for byte rate_dematch(convert_llr(demodulate(yi, yq, modulation, Kf).view(B, E), precision,
+        steps_per_unit), rv, out, accumulate) without the arrays in between.  steps_per_unit is the
+        quantiser's on a fixed codec and ignored otherwise.  After set_rate_matching."""
+        import torch
+
+        want = self._torch_dtypes()[0]
+        rv, E, M = int(rv), int(E), int(modulation)
+        if M not in (1, 2, 3, 4, 6):
+            raise ValueError(f"modulation must be 1, 2, 3, 4 or 6 bits per symbol, got {M}")
+        if E < 1 or E % M:
+            raise ValueError(f"E must be a positive multiple of modulation = {M}, got {E}")
+        self._check_in("yi", yi, (torch.float64,), E // M)
+        self._check_in("yq", yq, (torch.float64,), E // M)
+        if yq.shape != yi.shape:
+            raise ValueError(f"yi and yq must have one shape, got {tuple(yi.shape)} and {tuple(yq.shape)}")
+        B = yi.shape[0]
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate adds into `out`: pass the soft buffer")
+            out = torch.empty((B, stream_length(self.K)), dtype=want, device=yi.device)
+        else:
+            self._check_out("out", out, want, (B, stream_length(self.K)), yi.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(yi.device)
+        N.check(N.lib().td_demod_dematch(self._h, C.c_void_p(yi.data_ptr()), C.c_void_p(yq.data_ptr()), B, rv, E, M,
+                                         float(Kf), float(steps_per_unit), C.c_void_p(out.data_ptr()),
+                                         int(bool(accumulate)), C.c_void_p(stream.cuda_stream)))
+        return out
+
     # -- the transmit side: CRC-24 attach / check and the encoder (td_crc_set / td_crc_attach /
     #    td_crc_check / td_encode_device) ----------------------------------------------------
     def encode(self, info, out=None, stream=None):
@@ -551,6 +584,30 @@ def quantise(llr, steps_per_unit: float):
     import torch
 
     return torch.clamp(torch.round(llr * steps_per_unit), -127, 127).to(torch.int8)
+
+
+def convert_llr(llr, precision: str, steps_per_unit: float = 8.0, out=None, stream=None):
+    """td_llr_convert on the GPU: a float64 cuda tensor -> a tensor of the same shape in `precision`'s dtype
+    ("f64" a copy, "f32" the rounded narrowing, "fixed" the int8 clamp(rint(llr * steps_per_unit), +-127):
+    quantise's values on every finite input, in one kernel)."""
+    import torch
+
+    if precision not in _PRECS:
+        raise ValueError(f"precision must be one of {sorted(_PRECS)}, got {precision!r}")
+    want = {"f64": torch.float64, "f32": torch.float32, "fixed": torch.int8}[precision]
+    if llr.dtype != torch.float64 or not llr.is_cuda or not llr.is_contiguous():
+        raise ValueError(f"llr must be a contiguous float64 CUDA tensor, got {llr.dtype} {tuple(llr.shape)} on {llr.device}")
+    if out is None:
+        out = torch.empty(llr.shape, dtype=want, device=llr.device)
+    else:
+        TurboCodec._check_out("out", out, want, llr.shape, llr.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(llr.device)
+    if llr.numel():   # (an empty tensor has no address to pass)
+        with torch.cuda.device(llr.device):
+            N.check(N.lib().td_llr_convert(C.c_void_p(llr.data_ptr()), llr.numel(), _PRECS[precision], float(steps_per_unit),
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    return out
 
 
 def modulate(bits, modulation: int, stream=None):
