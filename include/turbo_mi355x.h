@@ -570,7 +570,7 @@ int td_count_errors(td_handle* h, const uint8_t* d_bits, int iters, const uint8_
  * declares rate_match / de_rate_match and the reference never defines them; the compat layer now does).
  * The coded stream s[0..3K+12) of encoderm_turbo (log_map.cpp:566-578) is the three LTE streams
  * interleaved, d_i(k) = s[3k+i], k < D = K+4 (the 12 tail values in order are d0_K, d1_K, d2_K, d0_K+1,
- * ... of 5.1.3.2.2); no filler bits.  Sub-block interleaver: 32 columns, R = ceil(D/32) rows, Kpi = 32R,
+ * ... of 5.1.3.2.2); no filler bits (a transport block's: td_tb_* below).  Sub-block interleaver: 32 columns, R = ceil(D/32) rows, Kpi = 32R,
  * ND = Kpi - D leading <NULL>s.  Circular buffer: Kw = 3 Kpi entries, of which a soft buffer of Ncb <= Kw
  * is used; a transmission of redundancy version rv reads the E non-NULL entries from
  * k0 = R (2 ceil(Ncb / 8R) rv + 2) on, wrapping round w[0..Ncb) for as long as needed (E above the
@@ -654,6 +654,92 @@ int td_crc_attach(td_handle* h, uint8_t* d_bits, int B, void* stream);
 /* d_rem[b] = td_crc24_host(row b of d_bits [B][K], K, poly): 0 = the block passes.  Launch and argument
  * rules as td_crc_attach. */
 int td_crc_check(td_handle* h, const uint8_t* d_bits, int B, uint32_t* d_rem, void* stream);
+
+/*
+ * Transport blocks (3GPP TS 36.212 5.1.2 code block segmentation with filler bits, 5.1.4.1.2 per-block rate
+ * matching sizes, 5.1.5 concatenation): the layer between a PDSCH / PUSCH transport block and the calls above,
+ * which take [B][K] rows of one K.  A td_tb owns only tables and is independent of any td_handle: the decode
+ * handles stay the caller's, one for K_minus and one for K_plus, created with the caller's own f1 / f2 (the LTE
+ * (K, f1, f2) table is not part of this library).  Not covered: scrambling, a demapper fused into
+ * td_tb_rate_dematch (use td_demodulate -> td_llr_convert on the whole [N][G] array), HARQ bookkeeping beyond
+ * `accumulate`.
+ *
+ * Plan (5.1.2): B = A + 24 bits (the transport block and its gCRC24A), Z = 6144.  B <= Z: L = 0, C = 1,
+ * B' = B; else L = 24, C = ceil(B / (Z - L)), B' = B + C L.  K_plus = the smallest code block size with
+ * C K >= B' (sizes by rule: 40..512 step 8, 528..1024 step 16, 1056..2048 step 32, 2112..6144 step 64).
+ * C = 1: C_plus = 1, K_minus = C_minus = 0.  Else K_minus = the next size below K_plus, C_minus =
+ * floor((C K_plus - B') / (K_plus - K_minus)), C_plus = C - C_minus.  F = C_plus K_plus + C_minus K_minus - B'
+ * filler bits (at most 63) open block 0.  Blocks r < C_minus have size K_minus, the others K_plus; each carries
+ * K_r - L bits of the B-bit sequence in order and, when C > 1, its gCRC24B in its last 24.
+ *
+ * Layout, block-major: block r of transport block n is row r N + n of the K_minus array [C_minus][N][K_minus]
+ * when r < C_minus, else row (r - C_minus) N + n of the K_plus array [C_plus][N][K_plus].  Each array is one
+ * batch for one decode handle (td_encode_device, td_decode_device, ... with B = C_minus N or C_plus N), and
+ * the rows that share the filler or an E are contiguous ranges.  The pointer of an array whose class is
+ * empty (C_minus = 0) may be null.
+ */
+typedef struct td_tb td_tb;
+typedef struct td_tb_plan {
+    int A, B, L, C, K_plus, K_minus, C_plus, C_minus, F;
+} td_tb_plan;
+typedef struct td_tb_params {
+    int A;               /* transport block size in bits, 1 .. 1048576 */
+    int Ncb_cap;         /* soft buffer limit: a block's Ncb = min(Ncb_cap, its Kw); 0 = the whole buffer,
+                            otherwise at least Kpi of K_plus */
+    int device;
+    double filler_llr;   /* what td_tb_rate_dematch writes for a filler bit: finite and <= 0 (the hard decision
+                            is LLR < 0 -> 0, so a known 0 is negative) */
+} td_tb_params;
+/* Host only (no GPU).  TD_EINVAL: A outside 1 .. 1048576, a null pointer. */
+int td_tb_plan_host(int A, td_tb_plan* out);
+/* Host only.  5.1.4.1.2 with G' = G / NlQm and gamma = G' mod C: blocks r < n_lo = C - gamma send
+ * E_lo = NlQm floor(G' / C) values, the others E_hi = NlQm ceil(G' / C).  Any pointer of the three may be
+ * null.  TD_EINVAL: a null plan, G or NlQm < 1, G >= 2^31, G no multiple of NlQm, G' < C. */
+int td_tb_rm_sizes_host(const td_tb_plan* p, long long G, int NlQm, int* E_lo, int* E_hi, int* n_lo);
+/* Host only: td_rm_index_host for a block whose first F bits are filler (0 <= F <= 63, F < K): their d0 and
+ * d1, stream positions 3k and 3k+1 with k < F, are <NULL> in the circular buffer and never selected; d2 stays,
+ * as in the standard.  k0(rv) is unchanged; only the non-NULL count and ordinals change.  F = 0:
+ * td_rm_index_host. */
+int td_rm_index_host_filler(int K, int Ncb, int F, int rv, int E, int32_t* idx);
+/* Builds and uploads the tables: the gCRC24A syndromes of length B, the gCRC24B syndromes of K_minus and
+ * K_plus, rank / pos of every class of block (K_minus, K_plus; with the filler's <NULL>s for block 0, and
+ * without).  It allocates and synchronises; after it no call does, every call is asynchronous on its stream
+ * and may be captured into a hipGraph, and pointers need only element alignment.
+ * TD_EINVAL: a null pointer, a bad A, Ncb_cap < 0 or 0 < Ncb_cap < Kpi(K_plus), filler_llr not finite or > 0,
+ * a bad device ordinal.  TD_ENODEV: no gfx950 device. */
+int td_tb_create(td_tb** out, const td_tb_params* p);
+int td_tb_destroy(td_tb* t);
+int td_tb_get_plan(const td_tb* t, td_tb_plan* out);
+/*
+ * The four device calls take N transport blocks each (N = 0 is a no-op).  TD_EINVAL -- a null td_tb, a null
+ * pointer of a non-empty class, N < 0, rv outside 0..3, G or NlQm that td_tb_rm_sizes_host rejects, an unknown
+ * precision -- changes nothing.
+ *
+ * td_tb_segment: d_tb [N][A] uint8 (any non-zero byte is a 1) -> the code blocks, every byte 0 or 1: F zeros
+ * open block 0, the blocks carry the A bits and their gCRC24A in order, and when C > 1 every block ends in the
+ * gCRC24B of its first K_r - 24 bits (the filler counted as zeros).  Two launches.
+ */
+int td_tb_segment(td_tb* t, const uint8_t* d_tb, int N, uint8_t* d_cb_minus, uint8_t* d_cb_plus, void* stream);
+/* d_coded_minus / d_coded_plus [rows][3K+12] uint8 = td_encode_device of the two arrays -> d_f [N][G]: row n is
+ * e_0 | e_1 | ... | e_{C-1} (5.1.5), e_r[k] = coded_r[idx_r[k]], k < E_r (td_tb_rm_sizes_host), idx_r =
+ * td_rm_index_host_filler(K_r, Ncb_r, r == 0 ? F : 0, rv, E_r).  One gather, one launch. */
+int td_tb_rate_match(td_tb* t, const uint8_t* d_coded_minus, const uint8_t* d_coded_plus, int N, int rv, long long G,
+                     int NlQm, uint8_t* d_f, void* stream);
+/* The transpose: d_f [N][G] soft values -> the blocks' soft buffers [rows][3K+12], all double (precision
+ * TD_F64), float (TD_F32) or int8 (TD_FIXED), with td_rate_dematch's arithmetic per block: sums in ascending
+ * k in the buffer's precision, int8 saturated to +-127 after every addition with -128 in the prior buffer read
+ * as -127, an unselected position kept (accumulate) or zero, no atomics, the same bytes on every run.  In
+ * block 0's rows, positions 3k and 3k+1 with k < F are always written with filler_llr as td_llr_convert
+ * would give it (int8: clamp(rint(filler_llr), -127, 127)).  d_f is what td_demodulate -> td_llr_convert give
+ * on the whole [N][G] array.  One launch. */
+int td_tb_rate_dematch(td_tb* t, const void* d_f, int precision, int N, int rv, long long G, int NlQm, void* d_llr_minus,
+                       void* d_llr_plus, int accumulate, void* stream);
+/* d_bits_minus / d_bits_plus [rows][K] uint8 = the decoders' hard decisions -> d_tb [N][A] (0 or 1), filler
+ * and CRCs stripped; d_cb_rem [N][C] = td_crc24_host of block r under gCRC24B with its first F bits (r = 0)
+ * taken as 0, and 0 when C = 1; d_tb_rem [N] = the gCRC24A remainder of the reassembled B bits.  Either
+ * remainder pointer may be null.  One launch, two with d_tb_rem. */
+int td_tb_concat(td_tb* t, const uint8_t* d_bits_minus, const uint8_t* d_bits_plus, int N, uint8_t* d_tb,
+                 uint32_t* d_cb_rem, uint32_t* d_tb_rem, void* stream);
 
 /* Last error message of this thread ("" if none). */
 const char* td_last_error(void);

@@ -34,6 +34,8 @@ EXPORTS = (
     "td_set_fixed_maxstar", "td_fixed_maxstar_table", "td_set_fixed_window_nii", "td_debug_workspace_fill",
     "td_encode_device", "td_crc_set", "td_crc_attach", "td_crc_check",
     "td_llr_convert", "td_demod_dematch",
+    "td_tb_plan_host", "td_tb_rm_sizes_host", "td_rm_index_host_filler", "td_tb_create", "td_tb_destroy",
+    "td_tb_get_plan", "td_tb_segment", "td_tb_rate_match", "td_tb_rate_dematch", "td_tb_concat",
 )
 
 
@@ -63,6 +65,14 @@ class TdFixedWindowParams(C.Structure):
 
 class TdFixedMaxstarParams(C.Structure):
     _fields_ = [("shift", C.c_int), ("corr", C.c_uint8 * 8)]
+
+
+class TdTbPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("A", "B", "L", "C", "K_plus", "K_minus", "C_plus", "C_minus", "F")]
+
+
+class TdTbParams(C.Structure):
+    _fields_ = [("A", C.c_int), ("Ncb_cap", C.c_int), ("device", C.c_int), ("filler_llr", C.c_double)]
 
 
 class TurboError(RuntimeError):
@@ -157,6 +167,18 @@ def lib() -> C.CDLL:
     if hasattr(L, "td_llr_convert"):   # the receive front end (older A/B builds loaded by TD_LIB_PATH lack it)
         L.td_llr_convert.argtypes = [P, C.c_longlong, I, C.c_double, P, P]
         L.td_demod_dematch.argtypes = [P, P, P, I, I, I, I, C.c_double, C.c_double, P, I, P]
+    if hasattr(L, "td_tb_create"):   # transport blocks (older A/B builds loaded by TD_LIB_PATH lack them)
+        LL = C.c_longlong
+        L.td_tb_plan_host.argtypes = [I, C.POINTER(TdTbPlan)]
+        L.td_tb_rm_sizes_host.argtypes = [C.POINTER(TdTbPlan), LL] + [I] + [C.POINTER(C.c_int)] * 3
+        L.td_rm_index_host_filler.argtypes = [I, I, I, I, I, P]
+        L.td_tb_create.argtypes = [C.POINTER(P), C.POINTER(TdTbParams)]
+        L.td_tb_destroy.argtypes = [P]
+        L.td_tb_get_plan.argtypes = [P, C.POINTER(TdTbPlan)]
+        L.td_tb_segment.argtypes = [P, P, I, P, P, P]
+        L.td_tb_rate_match.argtypes = [P, P, P, I, I, LL, I, P, P]
+        L.td_tb_rate_dematch.argtypes = [P, P, I, I, I, LL, I, P, P, I, P]
+        L.td_tb_concat.argtypes = [P, P, P, I, P, P, P, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

@@ -20,6 +20,7 @@
 #include "td_fixed.h"
 #include "td_kernels.h"
 #include "td_ratematch.h"
+#include "td_tb.h"
 
 #ifndef TD_SYS2_IN_TURBO
 #define TD_SYS2_IN_TURBO 1   // exact schedule: sys2 = sys1 o pi formed inside the turbo kernel (no demux_perm launch)
@@ -1813,20 +1814,36 @@ int td_demod_dematch(td_handle* h, const double* d_yi, const double* d_yq, int B
     return TD_OK;
 }
 
-int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx)
+namespace {
+
+// td_rm_index_host and td_rm_index_host_filler
+int rm_index(const char* who, int K, int Ncb, int F, int rv, int E, int32_t* idx)
 {
-    if (!idx) return fail(TD_EINVAL, "td_rm_index_host: null idx");
-    if (rv < 0 || rv > 3) return fail(TD_EINVAL, "td_rm_index_host: rv must be in 0..3");
-    if (E < 1) return fail(TD_EINVAL, "td_rm_index_host: E must be at least 1");
+    const std::string w(who);
+    if (!idx) return fail(TD_EINVAL, w + ": null idx");
+    if (rv < 0 || rv > 3) return fail(TD_EINVAL, w + ": rv must be in 0..3");
+    if (E < 1) return fail(TD_EINVAL, w + ": E must be at least 1");
     td::RmTables t;
-    if (!td::rm_build(K, Ncb, t))
-        return fail(TD_EINVAL, "td_rm_index_host: K must be in [1, 10000] and Ncb 0 or in [Kpi, Kw]");
+    if (!td::rm_build(K, Ncb, t, F))
+        return fail(TD_EINVAL, w + ": K must be in [1, 10000], Ncb 0 or in [Kpi, Kw], F in [0, 63] and below K");
     size_t j = (size_t)t.c0[rv];
     for (int k = 0; k < E; ++k) {
         idx[k] = t.pos[j];
         if (++j == (size_t)t.Nnn) j = 0;
     }
     return TD_OK;
+}
+
+}  // namespace
+
+int td_rm_index_host(int K, int Ncb, int rv, int E, int32_t* idx)
+{
+    return rm_index("td_rm_index_host", K, Ncb, 0, rv, E, idx);
+}
+
+int td_rm_index_host_filler(int K, int Ncb, int F, int rv, int E, int32_t* idx)
+{
+    return rm_index("td_rm_index_host_filler", K, Ncb, F, rv, E, idx);
 }
 
 
@@ -1897,6 +1914,265 @@ int td_crc_check(td_handle* h, const uint8_t* d_bits, int B, uint32_t* d_rem, vo
     if (!td::launch_crc_check) return fail(TD_EHIP, "td_crc_check: this build has no td_encode.hip");
     TD_HIP(hipSetDevice(h->p.device));
     TD_HIP(td::launch_crc_check(p, d_bits, d_rem, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+}  // extern "C"
+
+// ---- transport blocks (td_tb_core.h, td_tb.h) ----
+
+// Owns only tables.  Classes of code block: [K_plus?][with the filler's <NULL>s?]; the filler class exists
+// for the size of block 0 when F > 0.
+struct td_tb {
+    td_tb_params p{};
+    td::tb::Plan plan{};
+    int cus = 0;
+    uint32_t* d_syn_a = nullptr;
+    uint32_t* d_syn_b[2] = {nullptr, nullptr};
+    struct Class {
+        bool set = false;
+        int K = 0, R = 0, ND = 0, Nnn = 0, c0[4] = {};
+        int32_t* d_rank = nullptr;
+        int32_t* d_pos = nullptr;
+    } cls[2][2];
+};
+
+namespace {
+
+// finite and <= 0, judged on the bits (steps_ok's reason)
+bool filler_ok(double x)
+{
+    uint64_t u;
+    std::memcpy(&u, &x, sizeof u);
+    return ((u >> 52) & 0x7FF) != 0x7FF && ((u >> 63) != 0 || (u << 1) == 0);
+}
+
+template <typename T>
+hipError_t upload(T*& d, const std::vector<T>& v)
+{
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * v.size());
+    if (e != hipSuccess) {
+        d = nullptr;
+        return e;
+    }
+    return hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+}
+
+void to_c(const td::tb::Plan& p, td_tb_plan* o)
+{
+    *o = td_tb_plan{p.A, p.B, p.L, p.C, p.K_plus, p.K_minus, p.C_plus, p.C_minus, p.F};
+}
+
+// one launch's view; rv < 0: the calls that read no rate-matching table
+td::TbTables tb_view(const td_tb* t, int rv)
+{
+    td::TbTables v{};
+    v.plan = t->plan;
+    v.syn_a = t->d_syn_a;
+    v.syn_b[0] = t->d_syn_b[0], v.syn_b[1] = t->d_syn_b[1];
+    v.cus = t->cus;
+    if (rv >= 0)
+        for (int s = 0; s < 2; ++s)
+            for (int f = 0; f < 2; ++f) {
+                const td_tb::Class& c = t->cls[s][f];
+                if (c.set) v.cls[s][f] = td::TbRmClass{c.K, c.R, c.ND, c.Nnn, c.c0[rv], c.d_rank, c.d_pos};
+            }
+    return v;
+}
+
+// the checks the four device calls share: the handle, N, and a pointer for every non-empty class
+int tb_args(const char* who, const td_tb* t, int N, const void* minus, const void* plus)
+{
+    const std::string w(who);
+    if (!t) return fail(TD_EINVAL, w + ": null td_tb");
+    if (N < 0) return fail(TD_EINVAL, w + ": negative N");
+    if (!plus || (t->plan.C_minus > 0 && !minus)) return fail(TD_EINVAL, w + ": null pointer for a non-empty class of blocks");
+    return TD_OK;
+}
+
+int tb_rm_args(const char* who, const td_tb* t, int rv, long long G, int NlQm, td::tb::RmSizes& sz)
+{
+    const std::string w(who);
+    if (rv < 0 || rv > 3) return fail(TD_EINVAL, w + ": rv must be in 0..3");
+    if (!td::tb::rm_sizes(t->plan.C, G, NlQm, sz))
+        return fail(TD_EINVAL, w + ": G must be a multiple of NlQm >= 1 below 2^31 with G / NlQm >= C");
+    return TD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_tb_plan_host(int A, td_tb_plan* out)
+{
+    if (!out) return fail(TD_EINVAL, "td_tb_plan_host: null pointer");
+    td::tb::Plan p;
+    if (!td::tb::plan(A, p)) return fail(TD_EINVAL, "td_tb_plan_host: A must be in [1, 1048576]");
+    to_c(p, out);
+    return TD_OK;
+}
+
+int td_tb_rm_sizes_host(const td_tb_plan* p, long long G, int NlQm, int* E_lo, int* E_hi, int* n_lo)
+{
+    if (!p) return fail(TD_EINVAL, "td_tb_rm_sizes_host: null plan");
+    td::tb::RmSizes s;
+    if (!td::tb::rm_sizes(p->C, G, NlQm, s))
+        return fail(TD_EINVAL, "td_tb_rm_sizes_host: G must be a multiple of NlQm >= 1 below 2^31 with G / NlQm >= C >= 1");
+    if (E_lo) *E_lo = s.E_lo;
+    if (E_hi) *E_hi = s.E_hi;
+    if (n_lo) *n_lo = s.n_lo;
+    return TD_OK;
+}
+
+int td_tb_create(td_tb** out, const td_tb_params* p)
+{
+    if (!out || !p) return fail(TD_EINVAL, "td_tb_create: null argument");
+    *out = nullptr;
+    td::tb::Plan plan;
+    if (!td::tb::plan(p->A, plan)) return fail(TD_EINVAL, "td_tb_create: A must be in [1, 1048576]");
+    const int Kpi_plus = 32 * ((plan.K_plus + 4 + 31) / 32);
+    if (p->Ncb_cap < 0 || (p->Ncb_cap > 0 && p->Ncb_cap < Kpi_plus))
+        return fail(TD_EINVAL, "td_tb_create: Ncb_cap must be 0 or at least Kpi of K_plus = " + std::to_string(Kpi_plus));
+    if (!filler_ok(p->filler_llr)) return fail(TD_EINVAL, "td_tb_create: filler_llr must be finite and <= 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(TD_ENODEV, "td_tb_create: no HIP device visible");
+    if (p->device < 0 || p->device >= ndev) return fail(TD_EINVAL, "td_tb_create: device ordinal out of range");
+    hipDeviceProp_t prop;
+    TD_HIP(hipGetDeviceProperties(&prop, p->device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(TD_ENODEV, std::string("td_tb_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950");
+    TD_HIP(hipSetDevice(p->device));
+
+    td_tb* t = new td_tb();
+    t->p = *p, t->plan = plan, t->cus = prop.multiProcessorCount;
+    hipError_t e;
+    {
+        std::vector<uint32_t> syn((size_t)plan.B);
+        td::crc24_syndromes(plan.B, 0x864CFBu, syn.data());
+        e = upload(t->d_syn_a, syn);
+    }
+    const int Ks[2] = {plan.K_minus, plan.K_plus};
+    const int filler_size = plan.C_minus > 0 ? 0 : 1;   // block 0's
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        if (s == 0 && plan.C_minus == 0) continue;
+        if (plan.L) {
+            std::vector<uint32_t> syn((size_t)Ks[s]);
+            td::crc24_syndromes(Ks[s], 0x800063u, syn.data());
+            e = upload(t->d_syn_b[s], syn);
+        }
+        for (int f = 0; f < 2 && e == hipSuccess; ++f) {
+            if (f == 1 && (plan.F == 0 || s != filler_size)) continue;
+            td::RmTables rm;
+            const int Kw = 3 * 32 * ((Ks[s] + 4 + 31) / 32);
+            if (!td::rm_build(Ks[s], p->Ncb_cap == 0 || p->Ncb_cap > Kw ? 0 : p->Ncb_cap, rm, f ? plan.F : 0)) {
+                td_tb_destroy(t);
+                return fail(TD_EINVAL, "td_tb_create: no circular buffer for K = " + std::to_string(Ks[s]));
+            }
+            td_tb::Class& c = t->cls[s][f];
+            c.K = rm.K, c.R = rm.R, c.ND = rm.ND, c.Nnn = rm.Nnn;
+            for (int rv = 0; rv < 4; ++rv) c.c0[rv] = rm.c0[rv];
+            e = upload(c.d_rank, rm.rank);
+            if (e == hipSuccess) e = upload(c.d_pos, rm.pos);
+            c.set = e == hipSuccess;
+        }
+    }
+    if (e != hipSuccess) {
+        td_tb_destroy(t);
+        return e == hipErrorOutOfMemory ? fail(TD_ENOMEM, "td_tb_create: hipMalloc failed") : hip_fail(e, "td_tb_create: table upload");
+    }
+    *out = t;
+    return TD_OK;
+}
+
+int td_tb_destroy(td_tb* t)
+{
+    if (!t) return TD_OK;
+    (void)hipSetDevice(t->p.device);
+    if (t->d_syn_a) (void)hipFree(t->d_syn_a);
+    for (int s = 0; s < 2; ++s) {
+        if (t->d_syn_b[s]) (void)hipFree(t->d_syn_b[s]);
+        for (int f = 0; f < 2; ++f) {
+            if (t->cls[s][f].d_rank) (void)hipFree(t->cls[s][f].d_rank);
+            if (t->cls[s][f].d_pos) (void)hipFree(t->cls[s][f].d_pos);
+        }
+    }
+    delete t;
+    return TD_OK;
+}
+
+int td_tb_get_plan(const td_tb* t, td_tb_plan* out)
+{
+    if (!t || !out) return fail(TD_EINVAL, "td_tb_get_plan: null argument");
+    to_c(t->plan, out);
+    return TD_OK;
+}
+
+int td_tb_segment(td_tb* t, const uint8_t* d_tb, int N, uint8_t* d_cb_minus, uint8_t* d_cb_plus, void* stream)
+{
+    if (const int rc = tb_args("td_tb_segment", t, N, d_cb_minus, d_cb_plus)) return rc;
+    if (!d_tb) return fail(TD_EINVAL, "td_tb_segment: null d_tb");
+    if (N == 0) return TD_OK;
+    if (!td::launch_tb_segment) return fail(TD_EHIP, "td_tb_segment: this build has no td_tb.hip");
+    TD_HIP(hipSetDevice(t->p.device));
+    TD_HIP(td::launch_tb_segment(tb_view(t, -1), d_tb, N, d_cb_minus, d_cb_plus, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_tb_rate_match(td_tb* t, const uint8_t* d_coded_minus, const uint8_t* d_coded_plus, int N, int rv, long long G,
+                     int NlQm, uint8_t* d_f, void* stream)
+{
+    if (const int rc = tb_args("td_tb_rate_match", t, N, d_coded_minus, d_coded_plus)) return rc;
+    if (!d_f) return fail(TD_EINVAL, "td_tb_rate_match: null d_f");
+    td::tb::RmSizes sz;
+    if (const int rc = tb_rm_args("td_tb_rate_match", t, rv, G, NlQm, sz)) return rc;
+    if (N == 0) return TD_OK;
+    if (!td::launch_tb_rate_match) return fail(TD_EHIP, "td_tb_rate_match: this build has no td_tb.hip");
+    TD_HIP(hipSetDevice(t->p.device));
+    TD_HIP(td::launch_tb_rate_match(tb_view(t, rv), sz, G, d_coded_minus, d_coded_plus, N, d_f, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_tb_rate_dematch(td_tb* t, const void* d_f, int precision, int N, int rv, long long G, int NlQm, void* d_llr_minus,
+                       void* d_llr_plus, int accumulate, void* stream)
+{
+    if (const int rc = tb_args("td_tb_rate_dematch", t, N, d_llr_minus, d_llr_plus)) return rc;
+    if (!d_f) return fail(TD_EINVAL, "td_tb_rate_dematch: null d_f");
+    if (precision != TD_F64 && precision != TD_F32 && precision != TD_FIXED)
+        return fail(TD_EINVAL, "td_tb_rate_dematch: precision must be TD_F64, TD_F32 or TD_FIXED");
+    td::tb::RmSizes sz;
+    if (const int rc = tb_rm_args("td_tb_rate_dematch", t, rv, G, NlQm, sz)) return rc;
+    if (N == 0) return TD_OK;
+    if (!td::launch_tb_rate_dematch<double> || !td::launch_tb_rate_dematch<float> || !td::launch_tb_rate_dematch<int8_t>)
+        return fail(TD_EHIP, "td_tb_rate_dematch: this build has no td_tb.hip");
+    TD_HIP(hipSetDevice(t->p.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const td::TbTables v = tb_view(t, rv);
+    const double x = t->p.filler_llr;
+    if (precision == TD_F64)
+        TD_HIP(td::launch_tb_rate_dematch<double>(v, sz, G, static_cast<const double*>(d_f), N, static_cast<double*>(d_llr_minus),
+                                                  static_cast<double*>(d_llr_plus), x, accumulate, st));
+    else if (precision == TD_F32)
+        TD_HIP(td::launch_tb_rate_dematch<float>(v, sz, G, static_cast<const float*>(d_f), N, static_cast<float*>(d_llr_minus),
+                                                 static_cast<float*>(d_llr_plus), (float)x, accumulate, st));
+    else {
+        const double r = std::rint(x);   // td_llr_convert's int8 at one step a unit; x is finite and <= 0
+        TD_HIP(td::launch_tb_rate_dematch<int8_t>(v, sz, G, static_cast<const int8_t*>(d_f), N, static_cast<int8_t*>(d_llr_minus),
+                                                  static_cast<int8_t*>(d_llr_plus), (int8_t)(int)(r < -127.0 ? -127.0 : r),
+                                                  accumulate, st));
+    }
+    return TD_OK;
+}
+
+int td_tb_concat(td_tb* t, const uint8_t* d_bits_minus, const uint8_t* d_bits_plus, int N, uint8_t* d_tb,
+                 uint32_t* d_cb_rem, uint32_t* d_tb_rem, void* stream)
+{
+    if (const int rc = tb_args("td_tb_concat", t, N, d_bits_minus, d_bits_plus)) return rc;
+    if (!d_tb) return fail(TD_EINVAL, "td_tb_concat: null d_tb");
+    if (N == 0) return TD_OK;
+    if (!td::launch_tb_concat) return fail(TD_EHIP, "td_tb_concat: this build has no td_tb.hip");
+    TD_HIP(hipSetDevice(t->p.device));
+    TD_HIP(td::launch_tb_concat(tb_view(t, -1), d_bits_minus, d_bits_plus, N, d_tb, d_cb_rem, d_tb_rem,
+                                static_cast<hipStream_t>(stream)));
     return TD_OK;
 }
 

@@ -32,10 +32,13 @@ struct RmTables {
 constexpr int kRmPerm[32] = {0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30,
                              1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31};
 
-// Ncb: 0 = the whole buffer Kw, otherwise Kpi <= Ncb <= Kw.  False on a bad K or Ncb.
-inline bool rm_build(int K, int Ncb, RmTables& t)
+// Ncb: 0 = the whole buffer Kw, otherwise Kpi <= Ncb <= Kw.  F: the block's first F bits are filler (a
+// transport block's first code block, 36.212 5.1.2; 0 <= F <= 63 and F < K): their d0 and d1, stream positions
+// 3k and 3k+1 with k < F, are <NULL> in w; d2 stays, as in the standard.  False on a bad K, Ncb or F.
+inline bool rm_build(int K, int Ncb, RmTables& t, int F = 0)
 {
     if (K < 1 || K > 10000) return false;
+    if (F < 0 || F > 63 || F >= K) return false;
     const int D = K + 4, R = (D + 31) / 32, Kpi = 32 * R, Kw = 3 * Kpi, ND = Kpi - D;
     if (Ncb == 0) Ncb = Kw;
     if (Ncb < Kpi || Ncb > Kw) return false;
@@ -51,6 +54,7 @@ inline bool rm_build(int K, int Ncb, RmTables& t)
         w[Kpi + 2 * m] = 3 * k + 1;
         const int j2 = (j + Kpi - 1) % Kpi, m2 = inv[j2 % 32] * R + j2 / 32;   // v2 reads y one further on
         w[Kpi + 2 * m2 + 1] = 3 * k + 2;
+        if (k < F) w[m] = w[Kpi + 2 * m] = -1;
     }
     t.rank.assign(3 * D, -1);
     t.pos.clear();
