@@ -656,13 +656,42 @@ int td_crc_attach(td_handle* h, uint8_t* d_bits, int B, void* stream);
 int td_crc_check(td_handle* h, const uint8_t* d_bits, int B, uint32_t* d_rem, void* stream);
 
 /*
+ * Scrambling (3GPP TS 36.211 7.2, used by 6.3.1 PDSCH and 5.3.1 PUSCH): the length-31 Gold sequence
+ *   x1(n+31) = x1(n+3) ^ x1(n), x1(0) = 1, x1(1..30) = 0;
+ *   x2(n+31) = x2(n+3) ^ x2(n+2) ^ x2(n+1) ^ x2(n), x2(i) = bit i of c_init, i < 31;
+ *   c(n) = x1(n+1600) ^ x2(n+1600).
+ * The calls take no handle and run on the current device.  They are asynchronous on `stream`, allocate nothing
+ * and may be captured into a hipGraph; N = 0 or len = 0 is a no-op.  TD_EINVAL: a null pointer, N < 0, len < 0
+ * or len >= 2^31, an unknown precision.  Data pointers need only element alignment; d_seq is 4-byte aligned.
+ *
+ * td_gold_sequence: d_cinit [N] uint32 (bit 31 ignored) -> d_seq [N][W], W = (len + 31) / 32 words: bit g of
+ * row n is (d_seq[n W + (g >> 5)] >> (g & 31)) & 1 = c(g) for c_init = d_cinit[n]; bits >= len of the last
+ * word are 0.  Every thread jumps to its own offset (31 x 31 GF(2) matrices, built at compile time); none walks
+ * the sequence from 0.
+ */
+int td_gold_sequence(const uint32_t* d_cinit, int N, long long len, uint32_t* d_seq, void* stream);
+/* Host only (no GPU): the same W words for one c_init. */
+int td_gold_sequence_host(uint32_t cinit, long long len, uint32_t* seq);
+/* d_out[n][g] = (d_in[n][g] != 0) ^ c_n(g), each byte 0 or 1; [N][len] uint8; d_out may equal d_in. */
+int td_scramble(const uint8_t* d_in, const uint32_t* d_seq, int N, long long len, uint8_t* d_out, void* stream);
+/* Soft values [N][len] in `precision` (TD_F64 / TD_F32 / TD_FIXED int8): where c_n(g) = 1 the value's sign is
+ * flipped (IEEE negation, so 0.0 -> -0.0; int8: -128 read as -127, then negated), else copied.  In place
+ * allowed. */
+int td_descramble_llr(const void* d_in, int precision, const uint32_t* d_seq, int N, long long len, void* d_out,
+                      void* stream);
+
+/*
  * Transport blocks (3GPP TS 36.212 5.1.2 code block segmentation with filler bits, 5.1.4.1.2 per-block rate
  * matching sizes, 5.1.5 concatenation): the layer between a PDSCH / PUSCH transport block and the calls above,
  * which take [B][K] rows of one K.  A td_tb owns only tables and is independent of any td_handle: the decode
  * handles stay the caller's, one for K_minus and one for K_plus, created with the caller's own f1 / f2 (the LTE
- * (K, f1, f2) table is not part of this library).  Not covered: scrambling, a demapper fused into
- * td_tb_rate_dematch (use td_demodulate -> td_llr_convert on the whole [N][G] array), HARQ bookkeeping beyond
- * `accumulate`.
+ * (K, f1, f2) table is not part of this library).  Not covered: HARQ bookkeeping beyond `accumulate`, the
+ * PUSCH channel interleaver, c_init from RNTI / cell / slot (the caller passes it).
+ *
+ * The chain, transmit: td_tb_segment -> td_encode_device (two handles) -> td_tb_rate_match -> td_scramble (with
+ * td_gold_sequence's words) -> td_modulate.  Receive: td_tb_demod_dematch (symbols -> the two soft buffers,
+ * descrambled, in one launch) -> td_decode_device (two handles) -> td_tb_concat; or, call by call,
+ * td_demodulate -> td_descramble_llr -> td_llr_convert -> td_tb_rate_dematch, which gives the same bytes.
  *
  * Plan (5.1.2): B = A + 24 bits (the transport block and its gCRC24A), Z = 6144.  B <= Z: L = 0, C = 1,
  * B' = B; else L = 24, C = ceil(B / (Z - L)), B' = B + C L.  K_plus = the smallest code block size with
@@ -734,6 +763,17 @@ int td_tb_rate_match(td_tb* t, const uint8_t* d_coded_minus, const uint8_t* d_co
  * on the whole [N][G] array.  One launch. */
 int td_tb_rate_dematch(td_tb* t, const void* d_f, int precision, int N, int rv, long long G, int NlQm, void* d_llr_minus,
                        void* d_llr_plus, int accumulate, void* stream);
+/* Received symbols -> the blocks' soft buffers in one launch.  d_yi, d_yq [N][G / modulation] doubles; d_seq
+ * [N][(G + 31) / 32] words of td_gold_sequence, or null for no descrambling.  The result is, byte for byte,
+ * td_demodulate of all N G / modulation symbols with Kf, then (d_seq non-null) td_descramble_llr of that [N][G]
+ * double array, then td_llr_convert to `precision` with steps_per_unit, then td_tb_rate_dematch with the same
+ * t, precision, N, rv, G, NlQm and accumulate -- filler positions included -- without the [N][G] arrays in
+ * between.  The inputs are only read.  TD_EINVAL: everything td_tb_rate_dematch rejects, a null d_yi or d_yq,
+ * modulation not 1, 2, 3, 4 or 6, NlQm no multiple of modulation, and TD_FIXED with a steps_per_unit that is
+ * not finite or <= 0.  Allocates nothing and may be captured. */
+int td_tb_demod_dematch(td_tb* t, const double* d_yi, const double* d_yq, int precision, int N, int rv, long long G,
+                        int NlQm, int modulation, double Kf, double steps_per_unit, const uint32_t* d_seq,
+                        void* d_llr_minus, void* d_llr_plus, int accumulate, void* stream);
 /* d_bits_minus / d_bits_plus [rows][K] uint8 = the decoders' hard decisions -> d_tb [N][A] (0 or 1), filler
  * and CRCs stripped; d_cb_rem [N][C] = td_crc24_host of block r under gCRC24B with its first F bits (r = 0)
  * taken as 0, and 0 when C = 1; d_tb_rem [N] = the gCRC24A remainder of the reassembled B bits.  Either

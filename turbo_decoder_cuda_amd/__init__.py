@@ -6,8 +6,8 @@ codec interface (decoder.py).  See DESIGN.md.
 """
 from .decoder import (N_ITERATION, TERMINATED, TurboCodec, TurboCodingInit, convert_llr, demodulate, device_count,
                       fixed_maxstar_table, modulate, quantise, rate_match_index, stream_length)
-from .transport import TransportBlock, tb_plan
+from .transport import TransportBlock, descramble, gold_sequence, scramble, tb_plan
 
 __all__ = ["TurboCodec", "TurboCodingInit", "N_ITERATION", "TERMINATED", "device_count", "stream_length",
            "modulate", "demodulate", "rate_match_index", "quantise", "convert_llr", "fixed_maxstar_table",
-           "TransportBlock", "tb_plan"]
+           "TransportBlock", "tb_plan", "gold_sequence", "scramble", "descramble"]

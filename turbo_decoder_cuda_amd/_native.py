@@ -36,6 +36,7 @@ EXPORTS = (
     "td_llr_convert", "td_demod_dematch",
     "td_tb_plan_host", "td_tb_rm_sizes_host", "td_rm_index_host_filler", "td_tb_create", "td_tb_destroy",
     "td_tb_get_plan", "td_tb_segment", "td_tb_rate_match", "td_tb_rate_dematch", "td_tb_concat",
+    "td_gold_sequence", "td_gold_sequence_host", "td_scramble", "td_descramble_llr", "td_tb_demod_dematch",
 )
 
 
@@ -179,6 +180,13 @@ def lib() -> C.CDLL:
         L.td_tb_rate_match.argtypes = [P, P, P, I, I, LL, I, P, P]
         L.td_tb_rate_dematch.argtypes = [P, P, I, I, I, LL, I, P, P, I, P]
         L.td_tb_concat.argtypes = [P, P, P, I, P, P, P, P]
+    if hasattr(L, "td_gold_sequence"):   # scrambling (older A/B builds loaded by TD_LIB_PATH lack it)
+        LL = C.c_longlong
+        L.td_gold_sequence.argtypes = [P, I, LL, P, P]
+        L.td_gold_sequence_host.argtypes = [C.c_uint32, LL, P]
+        L.td_scramble.argtypes = [P, P, I, LL, P, P]
+        L.td_descramble_llr.argtypes = [P, I, P, I, LL, P, P]
+        L.td_tb_demod_dematch.argtypes = [P, P, P, I, I, I, LL, I, I, C.c_double, C.c_double, P, P, P, I, P]
     L.td_synth_modulation.argtypes = [P, I]
     L.td_modulate.argtypes = [P, C.c_longlong, I, P, P, P]
     L.td_demodulate.argtypes = [P, P, C.c_longlong, I, C.c_double, P, P]

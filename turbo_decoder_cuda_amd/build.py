@@ -73,7 +73,7 @@ def _workers(n: int) -> int:
 # config 5; the exact kernels (td_kernels.hip) lose 1 % under it and keep the default.
 WIN_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 SRCS = ("td_kernels.hip", "td_kernels_w12.hip", "td_kernels_win.hip", "td_synth.hip", "td_ratematch.hip", "td_fixed.hip",
-        "td_encode.hip", "td_tb.hip", "td_api.cpp")
+        "td_encode.hip", "td_tb.hip", "td_scramble.hip", "td_api.cpp")
 FILE_FLAGS = {"td_kernels_win.hip": WIN_FLAGS}
 
 

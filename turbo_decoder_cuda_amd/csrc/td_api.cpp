@@ -19,7 +19,9 @@
 #include "td_encode.h"
 #include "td_fixed.h"
 #include "td_kernels.h"
+#include "td_gold_core.h"
 #include "td_ratematch.h"
+#include "td_scramble.h"
 #include "td_tb.h"
 
 #ifndef TD_SYS2_IN_TURBO
@@ -1695,6 +1697,58 @@ int td_llr_convert(const double* d_in, long long n, int precision, double steps_
     return TD_OK;
 }
 
+// ---- scrambling (td_gold_core.h, td_scramble.h) ----
+
+int td_gold_sequence_host(uint32_t cinit, long long len, uint32_t* seq)
+{
+    if (!seq) return fail(TD_EINVAL, "td_gold_sequence_host: null pointer");
+    if (len < 0 || len > td::gold::kGoldMaxLen) return fail(TD_EINVAL, "td_gold_sequence_host: len must be in [0, 2^31)");
+    if (len == 0) return TD_OK;
+    td::gold::gold_words(td::gold::kGoldTables, cinit, len, 0, (len + 31) / 32, seq);
+    return TD_OK;
+}
+
+namespace {
+
+// the checks the three device calls share; rc < 0: nothing to do
+int scramble_args(const char* who, bool pointers, int N, long long len)
+{
+    const std::string w(who);
+    if (!pointers) return fail(TD_EINVAL, w + ": null pointer");
+    if (N < 0) return fail(TD_EINVAL, w + ": negative N");
+    if (len < 0 || len > td::gold::kGoldMaxLen) return fail(TD_EINVAL, w + ": len must be in [0, 2^31)");
+    return N == 0 || len == 0 ? -1 : TD_OK;
+}
+
+}  // namespace
+
+int td_gold_sequence(const uint32_t* d_cinit, int N, long long len, uint32_t* d_seq, void* stream)
+{
+    if (const int rc = scramble_args("td_gold_sequence", d_cinit && d_seq, N, len)) return rc < 0 ? TD_OK : rc;
+    if (!td::launch_gold_sequence) return fail(TD_EHIP, "td_gold_sequence: this build has no td_scramble.hip");
+    TD_HIP(td::launch_gold_sequence(d_cinit, N, len, d_seq, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_scramble(const uint8_t* d_in, const uint32_t* d_seq, int N, long long len, uint8_t* d_out, void* stream)
+{
+    if (const int rc = scramble_args("td_scramble", d_in && d_seq && d_out, N, len)) return rc < 0 ? TD_OK : rc;
+    if (!td::launch_scramble) return fail(TD_EHIP, "td_scramble: this build has no td_scramble.hip");
+    TD_HIP(td::launch_scramble(d_in, d_seq, N, len, d_out, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
+int td_descramble_llr(const void* d_in, int precision, const uint32_t* d_seq, int N, long long len, void* d_out, void* stream)
+{
+    if (precision != TD_F64 && precision != TD_F32 && precision != TD_FIXED)
+        return fail(TD_EINVAL, "td_descramble_llr: precision must be TD_F64, TD_F32 or TD_FIXED");
+    if (const int rc = scramble_args("td_descramble_llr", d_in && d_seq && d_out, N, len)) return rc < 0 ? TD_OK : rc;
+    if (!td::launch_descramble_llr) return fail(TD_EHIP, "td_descramble_llr: this build has no td_scramble.hip");
+    const int es = precision == TD_F64 ? 8 : precision == TD_F32 ? 4 : 1;
+    TD_HIP(td::launch_descramble_llr(d_in, es, d_seq, N, len, d_out, static_cast<hipStream_t>(stream)));
+    return TD_OK;
+}
+
 int td_count_errors(td_handle* h, const uint8_t* d_bits, int iters, const uint8_t* d_info, int B, int* d_err,
                     void* stream)
 {
@@ -1947,6 +2001,13 @@ bool filler_ok(double x)
     return ((u >> 52) & 0x7FF) != 0x7FF && ((u >> 63) != 0 || (u << 1) == 0);
 }
 
+// the filler's int8: td_llr_convert's at one step a unit; x is finite and <= 0
+int8_t filler_i8(double x)
+{
+    const double r = std::rint(x);
+    return (int8_t)(int)(r < -127.0 ? -127.0 : r);
+}
+
 template <typename T>
 hipError_t upload(T*& d, const std::vector<T>& v)
 {
@@ -2154,12 +2215,46 @@ int td_tb_rate_dematch(td_tb* t, const void* d_f, int precision, int N, int rv, 
     else if (precision == TD_F32)
         TD_HIP(td::launch_tb_rate_dematch<float>(v, sz, G, static_cast<const float*>(d_f), N, static_cast<float*>(d_llr_minus),
                                                  static_cast<float*>(d_llr_plus), (float)x, accumulate, st));
-    else {
-        const double r = std::rint(x);   // td_llr_convert's int8 at one step a unit; x is finite and <= 0
+    else
         TD_HIP(td::launch_tb_rate_dematch<int8_t>(v, sz, G, static_cast<const int8_t*>(d_f), N, static_cast<int8_t*>(d_llr_minus),
-                                                  static_cast<int8_t*>(d_llr_plus), (int8_t)(int)(r < -127.0 ? -127.0 : r),
-                                                  accumulate, st));
-    }
+                                                  static_cast<int8_t*>(d_llr_plus), filler_i8(x), accumulate, st));
+    return TD_OK;
+}
+
+int td_tb_demod_dematch(td_tb* t, const double* d_yi, const double* d_yq, int precision, int N, int rv, long long G,
+                        int NlQm, int modulation, double Kf, double steps_per_unit, const uint32_t* d_seq,
+                        void* d_llr_minus, void* d_llr_plus, int accumulate, void* stream)
+{
+    if (const int rc = tb_args("td_tb_demod_dematch", t, N, d_llr_minus, d_llr_plus)) return rc;
+    if (!d_yi || !d_yq) return fail(TD_EINVAL, "td_tb_demod_dematch: null symbols");
+    if (precision != TD_F64 && precision != TD_F32 && precision != TD_FIXED)
+        return fail(TD_EINVAL, "td_tb_demod_dematch: precision must be TD_F64, TD_F32 or TD_FIXED");
+    const int M = modulation;
+    if (M != 1 && M != 2 && M != 3 && M != 4 && M != 6)
+        return fail(TD_EINVAL, "td_tb_demod_dematch: modulation must be 1, 2, 3, 4 or 6");
+    td::tb::RmSizes sz;
+    if (const int rc = tb_rm_args("td_tb_demod_dematch", t, rv, G, NlQm, sz)) return rc;
+    if (NlQm % M)
+        return fail(TD_EINVAL, "td_tb_demod_dematch: NlQm = " + std::to_string(NlQm) + " is not a multiple of the modulation");
+    if (precision == TD_FIXED && !steps_ok(steps_per_unit))
+        return fail(TD_EINVAL, "td_tb_demod_dematch: steps_per_unit must be finite and positive");
+    if (N == 0) return TD_OK;
+    if (!td::launch_tb_demod_dematch<double> || !td::launch_tb_demod_dematch<float> || !td::launch_tb_demod_dematch<int8_t>)
+        return fail(TD_EHIP, "td_tb_demod_dematch: this build has no td_tb.hip");
+    TD_HIP(hipSetDevice(t->p.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const td::TbTables v = tb_view(t, rv);
+    const td::TbDemodArgs a{d_yi, d_yq, d_seq, M, Kf, steps_per_unit};
+    const double x = t->p.filler_llr;
+    if (precision == TD_F64)
+        TD_HIP(td::launch_tb_demod_dematch<double>(v, sz, G, a, N, static_cast<double*>(d_llr_minus),
+                                                   static_cast<double*>(d_llr_plus), x, accumulate, st));
+    else if (precision == TD_F32)
+        TD_HIP(td::launch_tb_demod_dematch<float>(v, sz, G, a, N, static_cast<float*>(d_llr_minus),
+                                                  static_cast<float*>(d_llr_plus), (float)x, accumulate, st));
+    else
+        TD_HIP(td::launch_tb_demod_dematch<int8_t>(v, sz, G, a, N, static_cast<int8_t*>(d_llr_minus),
+                                                   static_cast<int8_t*>(d_llr_plus), filler_i8(x), accumulate, st));
     return TD_OK;
 }
 

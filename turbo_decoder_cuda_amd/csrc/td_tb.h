@@ -42,6 +42,20 @@ template <typename T>
 __attribute__((weak)) hipError_t launch_tb_rate_dematch(const TbTables& t, const tb::RmSizes& sz, long long G, const T* d_f,
                                                         int N, T* d_llr_minus, T* d_llr_plus, T filler, int accumulate,
                                                         hipStream_t st);
+// td_tb_demod_dematch's received symbols: yi, yq [N][G / M]; seq [N][(G + 31) / 32] words of the scrambling
+// sequence, or null
+struct TbDemodArgs {
+    const double* yi;
+    const double* yq;
+    const uint32_t* seq;
+    int M;   // 1, 2, 3, 4 or 6; else hipErrorInvalidValue
+    double Kf, steps_per_unit;
+};
+// symbols -> soft buffers [..][N][3K+12]: launch_tb_rate_dematch of the demapped, descrambled, converted values
+template <typename T>
+__attribute__((weak)) hipError_t launch_tb_demod_dematch(const TbTables& t, const tb::RmSizes& sz, long long G,
+                                                         const TbDemodArgs& a, int N, T* d_llr_minus, T* d_llr_plus, T filler,
+                                                         int accumulate, hipStream_t st);
 // hard decisions [..][N][K] -> d_tb [N][A], d_cb_rem [N][C] (or null), d_tb_rem [N] (or null)
 __attribute__((weak)) hipError_t launch_tb_concat(const TbTables& t, const uint8_t* d_bits_minus, const uint8_t* d_bits_plus,
                                                   int N, uint8_t* d_tb, uint32_t* d_cb_rem, uint32_t* d_tb_rem, hipStream_t st);

@@ -17,6 +17,8 @@
 //                       gCRC24A bits are read back from the row), gCRC24B over both into the last 24
 //   td_tb_rate_match    one thread per element of the concatenated row: its block, its table, one gather
 //   td_tb_rate_dematch  td_dematch_band.h's body, a grid plane per code block
+//   td_tb_demod_dematch the same body and grid; where f would be read, the received symbol is demapped, its
+//                       sign flipped by the scrambling sequence's bit (td_gold_core.h) and converted
 //   td_tb_concat        tb_concat_kernel: a wave a code block: payload out, gCRC24B remainder;
 //                       tb_rem_kernel (only with d_tb_rem): a workgroup a transport block, gCRC24A remainder
 //                       of the blocks' payloads
@@ -25,6 +27,7 @@
 
 #include "td_dematch_band.h"
 #include "td_encode_core.h"
+#include "td_gold_core.h"
 #include "td_tb.h"
 
 namespace td {
@@ -232,6 +235,60 @@ __global__ __launch_bounds__(kTbThreads) void tb_rate_dematch_kernel(TbTables t,
     dematch_band<T, ACC, kTbRows>(rp, src, out, FillerFill<T>{fill ? p.F : 0, filler});
 }
 
+// td_tb_demod_dematch's source of block r: e_r[n][k] is bit g % M of symbol n (G / M) + g / M with g = e0 + k,
+// e0 = e_start(r) (a multiple of NlQm, so of M) -- demapped, its sign flipped by bit g of row n of seq (null:
+// no scrambling), converted.  The same double, the same negation and the same conversion as td_demodulate ->
+// td_descramble_llr -> td_llr_convert on the whole [N][G] array.  Consecutive k share a sequence word.
+template <int M, typename T>
+struct TbDemapRow {
+    const double* yi;      // the row's symbols
+    const double* yq;
+    const uint32_t* seq;   // the row's words, or null
+    unsigned e0;
+    double Kf, steps_per_unit;
+    __device__ __forceinline__ T operator[](size_t k) const
+    {
+        const unsigned g = e0 + (unsigned)k, s = g / (unsigned)M, b = g - s * (unsigned)M;
+        double x = demod_bit<M>(yi[s], yq[s], Kf, (int)b);
+        if (seq) x = gold::flip_sign(x, (seq[g >> 5] >> (g & 31)) & 1u);
+        return llr_to<T>(x, steps_per_unit);
+    }
+};
+template <int M, typename T>
+struct TbDemapSrc {
+    const double* yi;      // [N][G / M]
+    const double* yq;
+    const uint32_t* seq;   // [N][W] or null
+    size_t nsym, W;
+    unsigned e0;
+    double Kf, steps_per_unit;
+    __device__ __forceinline__ TbDemapRow<M, T> row(size_t n) const
+    {
+        return TbDemapRow<M, T>{yi + n * nsym, yq + n * nsym, seq ? seq + n * W : nullptr, e0, Kf, steps_per_unit};
+    }
+};
+
+// tb_rate_dematch_kernel with the symbols where f would be read
+template <int M, typename T, bool ACC>
+__global__ __launch_bounds__(kTbThreads) void tb_demod_dematch_kernel(TbTables t, tb::RmSizes sz, long long G, int N,
+                                                                      const double* __restrict__ yi,
+                                                                      const double* __restrict__ yq,
+                                                                      const uint32_t* __restrict__ seq, double Kf,
+                                                                      double steps_per_unit, T* llr_minus, T* llr_plus, T filler)
+{
+    const tb::Plan& p = t.plan;
+    const int r = blockIdx.z;
+    const bool plus = r >= p.C_minus, fill = r == 0 && p.F > 0;
+    const TbRmClass c = pick_class(t, plus, fill);
+    if ((int)blockIdx.x * kTbRows >= c.R) return;   // the whole workgroup: before any barrier
+    const RmParams rp{c.K, c.R, c.ND, c.Nnn, c.c0, tb::e_size(sz, r), N, c.rank, c.pos};
+    const size_t nout = 3 * (size_t)c.K + 12;
+    T* out = (plus ? llr_plus : llr_minus) + tb::block_row(p, r, 0, (size_t)N) * nout;
+    const TbDemapSrc<M, T> src{yi, yq, seq, (size_t)(G / M), (size_t)((G + 31) / 32), (unsigned)tb::e_start(sz, r), Kf,
+                               steps_per_unit};
+    dematch_band<T, ACC, kTbRows>(rp, src, out, FillerFill<T>{fill ? p.F : 0, filler});
+}
+
 // workgroups for `rows` rows, a wave each, at most four workgroups a compute unit
 unsigned row_wgs(size_t rows, int cus)
 {
@@ -282,6 +339,41 @@ hipError_t launch_tb_rate_dematch(const TbTables& t, const tb::RmSizes& sz, long
     return hipGetLastError();
 }
 
+namespace {
+
+template <int M, typename T>
+hipError_t launch_tb_demod_dematch_m(const TbTables& t, const tb::RmSizes& sz, long long G, const TbDemodArgs& a, int N,
+                                     T* d_llr_minus, T* d_llr_plus, T filler, int accumulate, hipStream_t st)
+{
+    // td_tb_rate_dematch's grid, cap included (crossed by tests/test_gpu_scramble.py at N = 513)
+    const int R = (t.plan.K_plus + 4 + 31) / 32;
+    const dim3 grid((unsigned)((R + kTbRows - 1) / kTbRows), (unsigned)N < kTbGridY ? (unsigned)N : kTbGridY,
+                    (unsigned)t.plan.C);
+    if (accumulate)
+        hipLaunchKernelGGL((tb_demod_dematch_kernel<M, T, true>), grid, dim3(kTbThreads), 0, st, t, sz, G, N, a.yi, a.yq, a.seq,
+                           a.Kf, a.steps_per_unit, d_llr_minus, d_llr_plus, filler);
+    else
+        hipLaunchKernelGGL((tb_demod_dematch_kernel<M, T, false>), grid, dim3(kTbThreads), 0, st, t, sz, G, N, a.yi, a.yq, a.seq,
+                           a.Kf, a.steps_per_unit, d_llr_minus, d_llr_plus, filler);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+template <typename T>
+hipError_t launch_tb_demod_dematch(const TbTables& t, const tb::RmSizes& sz, long long G, const TbDemodArgs& a, int N,
+                                   T* d_llr_minus, T* d_llr_plus, T filler, int accumulate, hipStream_t st)
+{
+    switch (a.M) {
+        case 1: return launch_tb_demod_dematch_m<1>(t, sz, G, a, N, d_llr_minus, d_llr_plus, filler, accumulate, st);
+        case 2: return launch_tb_demod_dematch_m<2>(t, sz, G, a, N, d_llr_minus, d_llr_plus, filler, accumulate, st);
+        case 3: return launch_tb_demod_dematch_m<3>(t, sz, G, a, N, d_llr_minus, d_llr_plus, filler, accumulate, st);
+        case 4: return launch_tb_demod_dematch_m<4>(t, sz, G, a, N, d_llr_minus, d_llr_plus, filler, accumulate, st);
+        case 6: return launch_tb_demod_dematch_m<6>(t, sz, G, a, N, d_llr_minus, d_llr_plus, filler, accumulate, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_tb_concat(const TbTables& t, const uint8_t* d_bits_minus, const uint8_t* d_bits_plus, int N, uint8_t* d_tb,
                             uint32_t* d_cb_rem, uint32_t* d_tb_rem, hipStream_t st)
 {
@@ -301,5 +393,11 @@ template hipError_t launch_tb_rate_dematch<float>(const TbTables&, const tb::RmS
                                                   float*, float, int, hipStream_t);
 template hipError_t launch_tb_rate_dematch<int8_t>(const TbTables&, const tb::RmSizes&, long long, const int8_t*, int, int8_t*,
                                                    int8_t*, int8_t, int, hipStream_t);
+template hipError_t launch_tb_demod_dematch<double>(const TbTables&, const tb::RmSizes&, long long, const TbDemodArgs&, int,
+                                                    double*, double*, double, int, hipStream_t);
+template hipError_t launch_tb_demod_dematch<float>(const TbTables&, const tb::RmSizes&, long long, const TbDemodArgs&, int,
+                                                   float*, float*, float, int, hipStream_t);
+template hipError_t launch_tb_demod_dematch<int8_t>(const TbTables&, const tb::RmSizes&, long long, const TbDemodArgs&, int,
+                                                    int8_t*, int8_t*, int8_t, int, hipStream_t);
 
 }  // namespace td

@@ -1,6 +1,8 @@
 """Transport blocks over the C ABI (td_tb_*; 3GPP TS 36.212 5.1.2, 5.1.4.1.2, 5.1.5): code block segmentation
 with filler bits and both CRCs, rate matching of a transport block's code blocks into one concatenated row, its
-soft transpose, and the reassembly.
+soft transpose, and the reassembly; and scrambling (td_gold_sequence, td_scramble, td_descramble_llr; 36.211 7.2)
+with the receive front end that demaps, descrambles, converts and de-rate-matches in one launch
+(TransportBlock.demod_dematch).
 
 The code blocks of N transport blocks live block-major in two tensors, [C_minus, N, K_minus] and
 [C_plus, N, K_plus]; viewed as [C N, K] each is one batch for one TurboCodec (encode, decode, ...).  A class
@@ -46,6 +48,88 @@ def rate_match_index_filler(K: int, Ncb: int, F: int, rv: int, E: int):
     idx = np.empty(int(E), dtype=np.int32)
     N.check(N.lib().td_rm_index_host_filler(int(K), int(Ncb), int(F), int(rv), int(E), C.c_void_p(idx.ctypes.data)))
     return idx
+
+
+def _cuda_in(name, t, dtypes, shape=None) -> None:
+    if t.dtype not in dtypes or not t.is_cuda or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous CUDA tensor of {' / '.join(map(str, dtypes))}"
+                         + (f" and shape {tuple(shape)}" if shape is not None else "")
+                         + f", got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _words(length: int) -> int:
+    return (int(length) + 31) // 32
+
+
+def _seq_stream(stream, device):
+    import torch
+
+    return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream)
+
+
+def gold_sequence(cinit, length: int, out=None, stream=None):
+    """The scrambling sequence of 36.211 7.2 (td_gold_sequence).  cinit: int32 [N] on the GPU, the 31 low bits of
+    each c_init (a uint32 viewed as int32; bit 31 is ignored) -> int32 [N, W], W = (length + 31) // 32: bit g of
+    row n is (seq[n, g >> 5] >> (g & 31)) & 1 = c(g); the last word's bits >= length are 0."""
+    import torch
+
+    _cuda_in("cinit", cinit, (torch.int32,), (cinit.shape[0],) if cinit.ndim == 1 else (-1,))
+    length = int(length)
+    if length < 0 or length >= 1 << 31:
+        raise ValueError(f"length must be in [0, 2^31), got {length}")
+    n, W = cinit.shape[0], _words(length)
+    if out is None:
+        out = torch.empty((n, W), dtype=torch.int32, device=cinit.device)
+    else:
+        _cuda_in("out", out, (torch.int32,), (n, W))
+    if n and length:
+        with torch.cuda.device(cinit.device):
+            N.check(N.lib().td_gold_sequence(C.c_void_p(cinit.data_ptr()), n, length, C.c_void_p(out.data_ptr()),
+                                             _seq_stream(stream, cinit.device)))
+    return out
+
+
+def _apply_seq(name, x, seq, out, dtypes):
+    _cuda_in(name, x, dtypes, (x.shape[0], x.shape[1]) if x.ndim == 2 else (-1, -1))
+    n, length = x.shape
+    import torch
+
+    _cuda_in("seq", seq, (torch.int32,), (n, _words(length)))
+    if seq.device != x.device:
+        raise ValueError(f"seq is on {seq.device}, {name} on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _cuda_in("out", out, (x.dtype,), (n, length))
+        if out.device != x.device:
+            raise ValueError(f"out is on {out.device}, {name} on {x.device}")
+    return n, length, out
+
+
+def scramble(bits, seq, out=None, stream=None):
+    """bits: uint8 [N, len] (any non-zero byte is a 1), seq: gold_sequence's int32 [N, (len + 31) // 32] ->
+    uint8 [N, len], (bit != 0) ^ c_n(g), every byte 0 or 1 (td_scramble).  out may be `bits`."""
+    import torch
+
+    n, length, out = _apply_seq("bits", bits, seq, out, (torch.uint8,))
+    if n and length:
+        with torch.cuda.device(bits.device):
+            N.check(N.lib().td_scramble(C.c_void_p(bits.data_ptr()), C.c_void_p(seq.data_ptr()), n, length,
+                                        C.c_void_p(out.data_ptr()), _seq_stream(stream, bits.device)))
+    return out
+
+
+def descramble(llr, seq, out=None, stream=None):
+    """llr: soft values [N, len], float64, float32 or int8 -> the same with the sign flipped where c_n(g) = 1
+    (0.0 -> -0.0; int8: -128 read as -127, then negated), copied elsewhere (td_descramble_llr).  out may be `llr`."""
+    import torch
+
+    n, length, out = _apply_seq("llr", llr, seq, out, (torch.float64, torch.float32, torch.int8))
+    if n and length:
+        with torch.cuda.device(llr.device):
+            N.check(N.lib().td_descramble_llr(C.c_void_p(llr.data_ptr()), _PRECISION[str(llr.dtype)], C.c_void_p(seq.data_ptr()),
+                                              n, length, C.c_void_p(out.data_ptr()), _seq_stream(stream, llr.device)))
+    return out
 
 
 class TransportBlock:
@@ -165,6 +249,40 @@ class TransportBlock:
         if n:
             N.check(N.lib().td_tb_rate_dematch(self._h, C.c_void_p(f.data_ptr()), _PRECISION[str(f.dtype)], n, int(rv), G,
                                                int(NlQm), pm, pp, int(bool(accumulate)), self._stream(stream, f.device)))
+        return out
+
+    def demod_dematch(self, yi, yq, rv: int, NlQm: int, modulation: int, Kf: float, precision: str,
+                      steps_per_unit: float = 8.0, seq=None, out=None, accumulate: bool = False, stream=None):
+        """yi, yq: the received symbols float64 [N, G / modulation] -> the (minus, plus) pair of soft buffers
+        [C, N, 3K+12] in `precision` ("f64", "f32" or "fixed": int8 at steps_per_unit) in one launch
+        (td_tb_demod_dematch): byte for byte rate_dematch(convert_llr(descramble(demodulate(yi, yq, modulation,
+        Kf).view(N, G), seq), precision, steps_per_unit), rv, NlQm, ...).  seq: gold_sequence's int32
+        [N, (G + 31) // 32], or None for no descrambling.  With accumulate the sums are added into `out`."""
+        import torch
+
+        dts = {"f64": torch.float64, "f32": torch.float32, "fixed": torch.int8}
+        if precision not in dts:
+            raise ValueError(f"precision must be one of {sorted(dts)}, got {precision!r}")
+        if modulation not in (1, 2, 3, 4, 6):
+            raise ValueError(f"modulation must be 1, 2, 3, 4 or 6 bits per symbol, got {modulation}")
+        self._in("yi", yi, (torch.float64,), (yi.shape[0], yi.shape[1]) if yi.ndim == 2 else (-1, -1))
+        self._in("yq", yq, (torch.float64,), yi.shape)
+        n, G = yi.shape[0], yi.shape[1] * int(modulation)
+        if int(NlQm) % int(modulation):
+            raise ValueError(f"NlQm = {NlQm} is not a multiple of the modulation {modulation}")
+        rm_sizes(self.plan, G, NlQm)   # raises on a bad G / NlQm
+        if seq is not None:
+            self._in("seq", seq, (torch.int32,), (n, _words(G)))
+        if out is None and accumulate:
+            raise ValueError("accumulate adds into `out`: pass the soft buffers")
+        out = self._pair_out(out, dts[precision], n, lambda K: 3 * K + 12, yi.device)
+        pm, pp = self._pair_in("out", out, (dts[precision],), n, lambda K: 3 * K + 12)
+        if n:
+            N.check(N.lib().td_tb_demod_dematch(self._h, C.c_void_p(yi.data_ptr()), C.c_void_p(yq.data_ptr()),
+                                                _PRECISION[str(dts[precision])], n, int(rv), G, int(NlQm), int(modulation),
+                                                float(Kf), float(steps_per_unit),
+                                                C.c_void_p(seq.data_ptr()) if seq is not None else None, pm, pp,
+                                                int(bool(accumulate)), self._stream(stream, yi.device)))
         return out
 
     def concat(self, bits, out=None, cb_rem=True, tb_rem=True, stream=None):
